@@ -2,6 +2,13 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cc NO_WAIT|WAIT_DIE|OCC|CALVIN]
                     [--config D|C|B] [--mpr 0.1] [--mpr-sweep 0,0.1,0.2,0.3,0.4,0.5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed
+step's outputs (--dump-outputs) and prints the headline line.  --full adds
+every other leg after it: the per-kernel table and roofline, stage times, the
+host-input, wire and closed-loop legs, the CPU baselines, TPC-C, configs B / C,
+the N>1 extras and the detail file.
 
 A step is one epoch through the hot path (probe -> sort -> decide -> execute)
 with its accesses already resident in HBM.  Default workload: config D of
@@ -133,6 +140,14 @@ def parse():
     ap.add_argument("--tpcc-txns", default="65536,10000",
                     help="txns per TPC-C epoch, comma-separated (the first is the leg's line; 10000 is the "
                          "reference's concurrency window, 8 nodes x 1250 in-flight txns)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: the per-kernel table and roofline, stage times, "
+                         "host-input, wire and closed-loop legs, CPU baselines, TPC-C, configs B / C, the N>1 "
+                         "extras, and the detail file (--detail-out); without it the run sets up, warms up, "
+                         "times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, what the last of them handed its caller as DIR/<name>.npy "
+                         "(dump_outputs); same arguments, same inputs, so two builds compare array for array")
     ap.add_argument("--timing", choices=["full", "kernel", "off"], default="off",
                     help="engine timing inside the timed region: per-stage events, only the "
                          "scatter/pass dispatch timestamps, or none (default: the timed region "
@@ -617,6 +632,46 @@ def timed(step, first, warmup, steps, world, batch=None):
     return stats, el
 
 
+DUMP_HOT_ROWS = 65_536                 # the partition's first rows: zipf's hottest keys
+DUMP_BLOCKS, DUMP_BLOCK_ROWS = 16, 4096  # + seeded blocks of rows over the whole partition
+DUMP_SEED = 0x5EED
+
+
+def _halves(u64):
+    """uint64 values as exact float64 pairs: [..., 0] the high 32 bits,
+    [..., 1] the low 32."""
+    u = np.ascontiguousarray(u64, dtype=np.uint64)
+    return np.stack([(u >> np.uint64(32)).astype(np.float64),
+                     (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(path, st, d_commit, n_commit, eng, rows):
+    """--dump-outputs: what the last timed step handed its caller (N>1: rank
+    0's), ~7 MB.
+    commit.npy        float32 [n_commit]: the step's commit bytes (1 committed, 0 aborted; an
+                      epoch group's: this rank's txns of each of its epochs)
+    stats.npy         float64 [7]: the step's dv_stats -- n_txn, n_acc, committed, aborted,
+                      write_cnt, read_digest (high, low 32 bits); the counters that do not
+                      depend on launch timing (an epoch group's count the whole group)
+    table_rows.npy    float64 [n]: the partition rows sampled -- the first DUMP_HOT_ROWS and
+                      DUMP_BLOCKS blocks of DUMP_BLOCK_ROWS rows at offsets drawn from DUMP_SEED
+    table_f0.npy      float64 [n, 2]: those rows' F0 fields after the step (high, low 32 bits),
+                      i.e. the executed writes of every epoch so far"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "commit.npy"), d_commit[:n_commit].cpu().numpy().astype(np.float32))
+    counters = np.array([st.n_txn, st.n_acc, st.committed, st.aborted, st.write_cnt], dtype=np.float64)
+    np.save(os.path.join(path, "stats.npy"), np.concatenate([counters, _halves([st.read_digest])[0]]))
+    rng = np.random.default_rng(DUMP_SEED)
+    hot = min(DUMP_HOT_ROWS, rows)
+    blk = min(DUMP_BLOCK_ROWS, rows)
+    starts = [0] + sorted(int(s) for s in rng.integers(0, rows - blk + 1, DUMP_BLOCKS))
+    sizes = [hot] + [blk] * DUMP_BLOCKS
+    np.save(os.path.join(path, "table_rows.npy"),
+            np.concatenate([np.arange(s, s + m, dtype=np.float64) for s, m in zip(starts, sizes)]))
+    np.save(os.path.join(path, "table_f0.npy"),
+            np.concatenate([_halves(eng.read_table(s, m)) for s, m in zip(starts, sizes)]))
+
+
 def pmc_traffic(a, cc_name, world, kernel):
     """HBM bytes per launch of `kernel` from the committed PMC summary
     (tools/pmc_summary.py), only if it was measured on these sources, this
@@ -909,6 +964,7 @@ class PartitionedBench:
         self.rows = rows
         self.d_commit = torch.zeros(max_txn_rank * world, dtype=torch.uint8, device="cuda")
         self.d_commits = [self.d_commit] + [torch.zeros_like(self.d_commit) for _ in self.lanes]
+        self.last_commit = self.d_commit  # the buffer of the last step run (--dump-outputs)
 
     def unorder(self):
         """After the timed region: the engine alone on the bench's stream
@@ -958,6 +1014,7 @@ class PartitionedBench:
             if lanes and self.lanes:
                 nl = len(self.d_commits)
                 base = self.eng._order_next
+                self.last_commit = self.d_commits[(base + count - 1) % nl]
                 return self.eng.run_epoch_groups_ordered(run, n_txn_rank,
                                                          [self.d_commits[(base + i) % nl] for i in range(count)])
             return self.eng.run_epoch_groups(run, n_txn_rank, self.d_commit)
@@ -1112,9 +1169,10 @@ def headline_record(out, detail_path=None):
         if isinstance(rec["config"].get(k), str):
             rec["config"][k] = rec["config"][k][:80]
     rf = out.get("roofline") or {}
-    rec["roofline"] = {k: _r(rf.get(k)) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
-                                                  "bytes_per_launch", "avg_launch_ms", "launches_per_epoch",
-                                                  "share_of_epoch")}
+    if "roofline" in out:  # (--full: it takes profiled epochs of its own)
+        rec["roofline"] = {k: _r(rf.get(k)) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac",
+                                                      "traffic", "bytes_per_launch", "avg_launch_ms",
+                                                      "launches_per_epoch", "share_of_epoch")}
     if isinstance(rf.get("k_probe"), dict):
         rec["roofline"]["k_probe"] = _pick(rf["k_probe"], ("kernel", "frac", "achieved", "avg_launch_ms"))
     cb = out.get("cpu_baseline")
@@ -1181,7 +1239,8 @@ def headline_record(out, detail_path=None):
     for k in ("extra_legs_error",):
         if k in out:
             legs[k] = str(out[k])[:200]
-    rec["legs"] = legs
+    if legs:
+        rec["legs"] = legs
     for k in ("src_hash", "timing_in_timed_region"):
         if k in out:
             rec[k] = out[k]
@@ -1290,14 +1349,10 @@ def main():
     # dv_epoch_group_run_batch (epoch groups); the other protocols step
     pipelined = not a.no_pipeline and (not part or a.protocol == "group")
     stats, el = timed(step, 0, a.warmup, a.steps, world, batch if pipelined else None)
-    # (the profiling legs time one context's launches: one lane)
-    if part:
-        pb.unorder()
-    pstats, sstats, ktimes = measure_legs(a, eng, step, a.warmup + a.steps, stats,
-                                          batch1 if pipelined else None)
-    table, kus = kernel_table(ktimes, pstats, rows, R, a, cc_name, world, world if (part and a.protocol == "group") else 1,
-                              tb=not part and not a.no_txn_begin, recs=not part and not a.no_txn_begin and not a.no_recs32)
+    if a.dump_outputs and rank == 0:  # (before any other leg reuses the commit buffer and the tables)
+        dump_outputs(a.dump_outputs, stats[-1], pb.last_commit if part else d_commit, n_txn_rank * world, eng, rows)
     committed = sum(s.committed for s in stats)  # global: every rank holds the same decisions
+    txns = sum(s.n_txn for s in stats)
     group = part and a.protocol == "group"
     out = {
         "metric": METRIC,
@@ -1335,13 +1390,37 @@ def main():
                                if group and a.order == "position" and cc_name != "CALVIN" else
                                "origin-major (Calvin's lock order)") if part else "one origin",
         },
-        "roofline": roofline(table, len(pstats), a),
+        "abort_rate": 1.0 - committed / max(1, txns),
+        "decided_txns_per_s": txns / el,
         "timing_in_timed_region": a.timing,
         "gen_seconds": t_gen,
         "src_hash": dvcc._lib.source_hash(),
     }
     if part and pb.lanes_refused:
         out["config"]["ordered_lanes_refused"] = pb.lanes_refused
+    if rank == 0:  # Deneva's [summary] line (stats.cpp:425-500) for scripts/helper.py, on stderr
+        from dvcc.stats import summary_line
+        # (partitioned runs do not count their multi-partition commits: those
+        # four counters are left out rather than printed as one-partition)
+        out["deneva_summary"] = summary_line(el, stats, part_counts=not part)
+        print(out["deneva_summary"], file=sys.stderr, flush=True)
+    if not a.full:  # the plain run ends here: the headline alone
+        if rank == 0:
+            print(headline_record(out), flush=True)
+        if part:
+            pb.unorder()
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # (the profiling legs time one context's launches: one lane)
+    if part:
+        pb.unorder()
+    pstats, sstats, ktimes = measure_legs(a, eng, step, a.warmup + a.steps, stats,
+                                          batch1 if pipelined else None)
+    table, kus = kernel_table(ktimes, pstats, rows, R, a, cc_name, world, world if group else 1,
+                              tb=not part and not a.no_txn_begin, recs=not part and not a.no_txn_begin and not a.no_recs32)
+    out["roofline"] = roofline(table, len(pstats), a)
     out.update(stage_summary(stats, sstats, table, el, R))
     out["kernels"] = table
     out["kernel_us_per_epoch"] = kus
@@ -1374,12 +1453,6 @@ def main():
             out["cpu_baseline_single_thread"] = single
         else:
             out["cpu_baseline"] = single
-    if rank == 0:  # Deneva's [summary] line (stats.cpp:425-500) for scripts/helper.py, on stderr
-        from dvcc.stats import summary_line
-        # (partitioned runs do not count their multi-partition commits: those
-        # four counters are left out rather than printed as one-partition)
-        out["deneva_summary"] = summary_line(el, stats, part_counts=not part)
-        print(out["deneva_summary"], file=sys.stderr, flush=True)
     if not part and not a.no_tpcc:
         out["tpcc"] = tpcc_leg(a)
     if not part and not a.no_configs and a.config == "D":

@@ -2,7 +2,8 @@
 the driver parses -- the headline keys, the dominant kernel's roofline and the
 CPU baseline -- with kernel tables and leg detail in the side file.  Built
 from round 4's full 29.7-KB record (which the driver could not parse) and from
-a synthetic N>1 record; no GPU."""
+a synthetic N>1 record; no GPU.  Beside them the plain run (no --full): its
+record, --dump-outputs on a stand-in engine, and one short run on the GPU."""
 import json
 import os
 import sys
@@ -50,6 +51,96 @@ def test_round4_record_compacts_under_the_limit(tmp_path):
                                                                      rel=1e-3)
     assert "window_10000_CALVIN" in legs["tpcc"]
     assert legs["cpu_config_a"]["cores"] == 4
+
+
+def test_plain_record_is_the_headline_alone():
+    """A run without --full: the contract's keys and the config, no roofline,
+    legs, CPU baseline or detail file."""
+    out = {"metric": bench.METRIC, "value": 1.4e8, "unit": "committed txns/s", "n_gpus": 1, "steps": 20,
+           "warmup": 5, "ms_per_step": 0.1768, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "u64", "data": "synthetic", "config": {"workload": "w", "cc_alg": "NO_WAIT"},
+           "abort_rate": 0.977, "decided_txns_per_s": 5.9e9, "src_hash": "abc", "deneva_summary": "[summary] x"}
+    line = bench.headline_record(out)
+    assert "\n" not in line and len(line) < bench.LINE_LIMIT
+    rec = json.loads(line)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert rec[k] == pytest.approx(out[k], rel=1e-3) if isinstance(out[k], float) else rec[k] == out[k], k
+    for k in ("roofline", "legs", "cpu_baseline", "detail"):
+        assert k not in rec, k
+
+
+def test_full_is_opt_in(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs on a stand-in engine: float32 / float64 arrays, u64
+    values exact as 32-bit halves, the same rows sampled every time."""
+    import numpy as np
+    import torch
+    rows = 1 << 20
+
+    class Eng:
+        def read_table(self, first, n):
+            return (np.arange(first, first + n, dtype=np.uint64) << np.uint64(40)) | np.uint64(0xFFFFFFFF)
+
+    class St:
+        n_txn, n_acc, committed, aborted, write_cnt, read_digest = 1000, 10_000, 3, 997, 15, (1 << 64) - 2
+
+    commit = torch.zeros(1024, dtype=torch.uint8)
+    commit[[1, 5, 999]] = 1
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), St, commit, 1000, Eng(), rows)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["commit.npy", "stats.npy", "table_f0.npy", "table_rows.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert got["commit.npy"].shape == (1000,) and got["commit.npy"].sum() == 3
+    assert got["stats.npy"].tolist() == [1000, 10_000, 3, 997, 15, 0xFFFFFFFF, 0xFFFFFFFE]
+    r = got["table_rows.npy"].astype(np.uint64)
+    n = bench.DUMP_HOT_ROWS + bench.DUMP_BLOCKS * bench.DUMP_BLOCK_ROWS
+    assert r.shape == (n,) and r.max() < rows and (r[:bench.DUMP_HOT_ROWS] == np.arange(bench.DUMP_HOT_ROWS)).all()
+    f0 = got["table_f0.npy"].astype(np.uint64)
+    assert f0.shape == (n, 2)
+    assert (((f0[:, 0] << np.uint64(32)) | f0[:, 1]) == Eng().read_table(0, rows)[r]).all()
+    for f, v in got.items():
+        assert (np.load(tmp_path / "b" / f) == v).all(), f
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps(tmp_path):
+    """bench.py as every pull request runs it: one JSON line on stdout, K timed
+    steps, no side legs, and the last step's outputs consistent with each other."""
+    import subprocess
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=120,
+                       cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert (rec["metric"], rec["unit"], rec["dtype"], rec["higher_is_better"]) == \
+        (bench.METRIC, "committed txns/s", "u64", True)
+    assert (rec["steps"], rec["warmup"], rec["n_gpus"]) == (3, 1, 1)
+    assert rec["ms_per_step"] > 0
+    n_txn = rec["config"]["txns_per_epoch"]
+    # value = committed / s over the timed steps: abort_rate ties it to ms_per_step (the line's
+    # numbers carry 4 digits: abort_rate ~0.977 +- 5e-5 is +- 0.22 % of the committed share)
+    assert rec["value"] == pytest.approx((1 - rec["abort_rate"]) * n_txn / (rec["ms_per_step"] * 1e-3), rel=5e-3)
+    for k in ("roofline", "legs", "cpu_baseline", "detail"):
+        assert k not in rec, k
+    assert os.listdir(tmp_path) == ["out"]  # (no detail file, nothing else written)
+    commit, st = np.load(tmp_path / "out" / "commit.npy"), np.load(tmp_path / "out" / "stats.npy")
+    assert commit.dtype == np.float32 and commit.shape == (n_txn,) and set(np.unique(commit)) <= {0.0, 1.0}
+    assert st[0] == n_txn and st[2] == commit.sum(dtype=np.float64) and st[2] + st[3] == n_txn and st[2] > 0
+    f0 = np.load(tmp_path / "out" / "table_f0.npy")
+    assert f0.dtype == np.float64 and f0.shape == (len(np.load(tmp_path / "out" / "table_rows.npy")), 2)
 
 
 def test_synthetic_multi_gpu_record():

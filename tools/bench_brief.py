@@ -15,6 +15,8 @@ if "value" not in d:  # (--tpcc-only: the TPC-C leg alone)
                 print(f"tpcc {size or 'main'} {cc}: {v['ms_per_epoch']:.4f} ms/epoch, {v['committed_per_s']:.4g} committed/s")
     sys.exit(0)
 print(f"value {d['value']:.4g} {d['unit']}  ms/step {d['ms_per_step']:.4f}  abort {d.get('abort_rate', 0):.4f}")
+if "roofline" not in d:  # (a run without --full: the headline alone)
+    sys.exit(0)
 r = d["roofline"]
 print(f"roofline {r['kernel']}: {r['achieved']:.1f} GB/s frac {r['frac']:.4f} share {r.get('share_of_epoch', 0):.3f}")
 if "k_probe" in r:

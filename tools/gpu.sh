@@ -30,7 +30,7 @@ run_one() {
         || { tail -30 $out/smoke.log; return 1; }
     tail -3 $out/smoke.log ;;
   bench)
-    timeout -k 10 900 python -u bench.py --detail-out $out/bench_detail.json "$@" > $out/bench.json 2> $out/bench.err \
+    timeout -k 10 900 python -u bench.py --full --detail-out $out/bench_detail.json "$@" > $out/bench.json 2> $out/bench.err \
         || { tail -30 $out/bench.err; return 1; }
     python3 tools/bench_brief.py $out/bench.json ;;
   ab)
@@ -39,7 +39,7 @@ run_one() {
   prof)
     (cd /tmp && export TMPDIR=/tmp)
     export TMPDIR=/tmp
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -T -d $out/kt -o run -- python3 bench.py "$@" \
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -T -d $out/kt -o run -- python3 bench.py --full "$@" \
         > $out/kt_bench.json 2> $out/kt.err || { tail -30 $out/kt.err; return 1; }
     local kt=$(find $out/kt -name 'run_kernel_stats.csv' | head -1)
     head -25 $kt ;;
@@ -47,7 +47,7 @@ run_one() {
     export TMPDIR=/tmp
     local kernels=$1; shift
     for c in FETCH_SIZE WRITE_SIZE; do
-      timeout -s KILL 180 rocprofv3 --pmc $c -f csv -T -d $out/pmc_$c -o run -- python3 bench.py "$@" \
+      timeout -s KILL 180 rocprofv3 --pmc $c -f csv -T -d $out/pmc_$c -o run -- python3 bench.py --full "$@" \
           > $out/pmc_$c.json 2> $out/pmc_$c.err || { tail -20 $out/pmc_$c.err; return 1; }
     done
     local src=$(python3 -c "import sys; sys.path.insert(0, 'deneva-plus_amd'); from dvcc import _lib; print(_lib.source_hash())")

@@ -4,7 +4,7 @@
 set -e
 OUT=gpurun_out/$1; shift
 mkdir -p $OUT
-DVCC_HOST_PROF=1 timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-configs --no-tpcc "$@" > $OUT/b.json 2> $OUT/b.err
+DVCC_HOST_PROF=1 timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-configs --no-tpcc "$@" > $OUT/b.json 2> $OUT/b.err
 grep "dvcc host" $OUT/b.err > $OUT/host_prof.txt || true
 python3 tools/bench_brief.py $OUT/b.json | head -1
 cat $OUT/host_prof.txt

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for v in $LIBS; do
   DVCC_LIB=$PWD/exp_build/$v/libdvcc.so timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/$v -o run \
-      -- python3 bench.py --steps 10 --warmup 2 --epochs 2 --no-cpu-baseline --no-tpcc > $OUT/$v.json 2> $OUT/$v.err
+      -- python3 bench.py --full --steps 10 --warmup 2 --epochs 2 --no-cpu-baseline --no-tpcc > $OUT/$v.json 2> $OUT/$v.err
   python3 - "$OUT/$v/run_kernel_stats.csv" "$KS" "$v" <<'PY'
 import csv, sys
 want = sys.argv[2].split(",")
