@@ -8,7 +8,9 @@
 // renumbered from 0, to open the next epoch ahead of the new txns -- they are
 // older, so they keep their priority (WAIT_DIE keeps a restarted txn's
 // timestamp).  Three launches: per-block counts, one scan of the block
-// counts, then every carried txn copies its accesses.
+// counts, then every carried txn copies its accesses.  A TPC-C epoch carries
+// a fifth stream beside key, type, table and txn id: each access's 8-byte
+// operation word (ARGS; the YCSB instantiations hold no trace of it).
 #include "dvcc_common.h"
 
 namespace dvcc {
@@ -92,6 +94,7 @@ __global__ __launch_bounds__(kBlock) void k_carry_scan(uint32_t *__restrict__ bt
 // holds 64 consecutive txns, whose carried accesses are contiguous in the
 // output: its lanes copy them together (a prefix sum of the lengths picks
 // each access's txn), so reads and writes are coalesced.
+template <bool ARGS>
 __global__ __launch_bounds__(kBlock) void k_carry_copy(
     const uint8_t *__restrict__ status, const uint32_t *__restrict__ tb_start,
     const uint32_t *__restrict__ tb_end, uint32_t n_txn, const uint32_t *__restrict__ bt,
@@ -99,7 +102,8 @@ __global__ __launch_bounds__(kBlock) void k_carry_copy(
     const uint8_t *__restrict__ types, const uint8_t *__restrict__ tables, uint64_t *__restrict__ okeys,
     uint8_t *__restrict__ otypes, uint32_t *__restrict__ otxn, uint8_t *__restrict__ otables,
     uint32_t *__restrict__ tot, const uint32_t *__restrict__ skip, const uint32_t *__restrict__ recs,
-    uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb) {
+    uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb, const uint64_t *__restrict__ args,
+    uint64_t *__restrict__ oargs) {
     __shared__ uint32_t lds4[4];
     if (skip && *skip) return;  // (a refill behind a halted epoch: k_refill_plan)
     const uint32_t lane = threadIdx.x & 63;
@@ -171,6 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_carry_copy(
             otypes[o] = types[i];
             otxn[o] = sid;
             if (tables) otables[o] = tables[i];
+            if (ARGS) oargs[o] = args[i];  // (TPC-C: the operation word, an 8-byte stream like the keys)
         }
         return;
     }
@@ -205,6 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_carry_copy(
         otypes[o] = types[in];
         otxn[o] = sid;
         if (tables) otables[o] = tables[in];
+        if (ARGS) oargs[o] = args[in];
     }
 }
 
@@ -261,6 +267,7 @@ __global__ void k_refill_plan(const uint8_t *__restrict__ status, uint32_t n_txn
 // the fresh txns [cur, cur + F) of the pool (wrapping), renumbered after the
 // C carried ones, their accesses after the carried accesses; the epoch's
 // access count into *n_acc_dev
+template <bool ARGS>
 __global__ __launch_bounds__(kBlock) void k_refill_fresh(const uint64_t *__restrict__ keys,
                                                          const uint8_t *__restrict__ types,
                                                          const uint8_t *__restrict__ tables,
@@ -271,7 +278,9 @@ __global__ __launch_bounds__(kBlock) void k_refill_fresh(const uint64_t *__restr
                                                          uint32_t *__restrict__ otxn, uint8_t *__restrict__ otables,
                                                          uint32_t *__restrict__ n_acc_dev,
                                                          const uint32_t *__restrict__ precs,
-                                                         uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb) {
+                                                         uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb,
+                                                         const uint64_t *__restrict__ pargs,
+                                                         uint64_t *__restrict__ oargs) {
     if (tot[4]) return;
     const uint32_t C = tot[2] < n_out ? tot[2] : n_out, A = tot[1], cur = tot[3], F = tot[5];
     const uint32_t e1 = cur + F < pool_n ? cur + F : pool_n;     // [cur, e1) then [0, F - (e1 - cur))
@@ -295,6 +304,7 @@ __global__ __launch_bounds__(kBlock) void k_refill_fresh(const uint64_t *__restr
         otypes[A + i] = types[src];
         otxn[A + i] = C + t;
         if (otables) otables[A + i] = tables ? tables[src] : 0;
+        if (ARGS) oargs[A + i] = pargs[src];
     }
 }
 
@@ -304,19 +314,30 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    const uint32_t *ptb, uint32_t pool_n, uint32_t *cursor, uint32_t n_out, uint64_t fresh_bound,
                    uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
                    uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs,
-                   const uint32_t *precs, uint32_t *orecs, uint32_t *otb) {
+                   const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const uint64_t *args,
+                   const uint64_t *pargs, uint64_t *oargs) {
     const uint32_t nb = carry_blocks(n_txn);
     if (nb) {
         DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba);
         DV_LAUNCH(k_carry_scan, 1, kBlock, 0, s, bt, ba, nb);
     }
     DV_LAUNCH(k_refill_plan, 1, 64, 0, s, status, n_txn, bt, nb, tot, n_out, cursor, pool_n, ctr);
-    if (nb)
-        DV_LAUNCH(k_carry_copy, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, n_out, keys, types, tables,
-                  okeys, otypes, otxn, otables, tot, (const uint32_t *)(tot + 4), recs, orecs, otb);
+    const uint32_t *skip = tot + 4;
+    const uint64_t *no_args = nullptr;
+    if (nb && oargs)
+        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, n_out, keys, types,
+                  tables, okeys, otypes, otxn, otables, tot, skip, recs, orecs, otb, args, oargs);
+    else if (nb)
+        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, n_out, keys, types,
+                  tables, okeys, otypes, otxn, otables, tot, skip, recs, orecs, otb, no_args, oargs);
     const uint64_t g = (fresh_bound + kBlock - 1) / kBlock;
-    DV_LAUNCH(k_refill_fresh, (uint32_t)(g < 1 ? 1 : (g > 4096 ? 4096 : g)), kBlock, 0, s, pkeys, ptypes, ptables,
-              ptxn, ptb, pool_n, tot, n_out, okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb);
+    const uint32_t grid = (uint32_t)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+    if (oargs)
+        DV_LAUNCH((k_refill_fresh<true>), grid, kBlock, 0, s, pkeys, ptypes, ptables, ptxn, ptb, pool_n, tot, n_out,
+                  okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb, pargs, oargs);
+    else
+        DV_LAUNCH((k_refill_fresh<false>), grid, kBlock, 0, s, pkeys, ptypes, ptables, ptxn, ptb, pool_n, tot, n_out,
+                  okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb, no_args, oargs);
 }
 
 // a client batch's per-txn access ranges from its acc_txn (non-decreasing;
@@ -351,7 +372,8 @@ uint32_t carry_blocks(uint32_t n_txn) { return n_txn ? (n_txn + kCarryTpb - 1) /
 void launch_carry(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
                   uint32_t n_txn, uint32_t max_txn, const uint64_t *keys, const uint8_t *types,
                   const uint8_t *tables, uint64_t *okeys, uint8_t *otypes, uint32_t *otxn,
-                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot) {
+                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot, const uint64_t *args,
+                  uint64_t *oargs) {
     const uint32_t nb = carry_blocks(n_txn);
     if (!nb) {
         (void)hipMemsetAsync(tot, 0, 3 * sizeof(uint32_t), s);
@@ -360,9 +382,14 @@ void launch_carry(hipStream_t s, const uint8_t *status, const uint32_t *tb_start
     DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba);
     DV_LAUNCH(k_carry_scan, 1, kBlock, 0, s, bt, ba, nb);
     DV_LAUNCH(k_carry_total, 1, 64, 0, s, status, n_txn, bt, nb, tot);
-    DV_LAUNCH(k_carry_copy, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, max_txn, keys, types, tables,
-                                       okeys, otypes, otxn, otables, tot, (const uint32_t *)nullptr,
-                                       (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    const uint32_t *none = nullptr;
+    uint32_t *onone = nullptr;
+    if (oargs)
+        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, max_txn, keys,
+                  types, tables, okeys, otypes, otxn, otables, tot, none, none, onone, onone, args, oargs);
+    else
+        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, max_txn, keys,
+                  types, tables, okeys, otypes, otxn, otables, tot, none, none, onone, onone, args, oargs);
 }
 
 }  // namespace dvcc

@@ -566,11 +566,13 @@ namespace dvcc {
 // not committed, in sequence order and renumbered from 0, capped at max_txn
 // txns, into o*; tot (3 words, device) = carried txns, their accesses, and the
 // carried txns before the cap.  bt/ba: carry_blocks(n_txn) words each.
+// oargs (TPC-C): the carried accesses' operation words too, from args.
 uint32_t carry_blocks(uint32_t n_txn);
 void launch_carry(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
                   uint32_t n_txn, uint32_t max_txn, const uint64_t *keys, const uint8_t *types,
                   const uint8_t *tables, uint64_t *okeys, uint8_t *otypes, uint32_t *otxn,
-                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot);
+                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot, const uint64_t *args = nullptr,
+                  uint64_t *oargs = nullptr);
 
 // per-txn access ranges of a batch from its acc_txn (dv_epoch_group_carry)
 void launch_txn_ranges(hipStream_t s, const uint32_t *acc_txn, uint64_t n, uint32_t n_txn, uint32_t *tbs,
@@ -585,7 +587,9 @@ void launch_txn_ranges(hipStream_t s, const uint32_t *acc_txn, uint64_t n, uint3
 // every kernel a no-op.  tot: kRefillTot words.  tb form (orecs, otb): the
 // next epoch as 4-byte records (recs: the previous epoch's, precs: the
 // pool's) and its txn boundaries otb[0..n_out]; okeys NULL: only that form
-// (o{keys,types,txn,tables} are not written).
+// (o{keys,types,txn,tables} are not written).  oargs (TPC-C, never with the
+// tb form): the operation words of the carried (args) and fresh (pargs)
+// accesses too.
 constexpr uint32_t kRefillTot = 6;
 void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
                    uint32_t n_txn, const uint64_t *keys, const uint8_t *types, const uint8_t *tables,
@@ -593,7 +597,8 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    const uint32_t *ptb, uint32_t pool_n, uint32_t *cursor, uint32_t n_out, uint64_t fresh_bound,
                    uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
                    uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs = nullptr,
-                   const uint32_t *precs = nullptr, uint32_t *orecs = nullptr, uint32_t *otb = nullptr);
+                   const uint32_t *precs = nullptr, uint32_t *orecs = nullptr, uint32_t *otb = nullptr,
+                   const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr);
 
 // ---- prefix-kill epochs (dvcc_prefix.hip)
 // the row-state bitmap (2 bits per row): its 32-bit words for `rows` rows;

@@ -121,6 +121,8 @@ struct dv_ctx {
     uint64_t tp_dsnap_cap = 0;
     const uint64_t *tp_args = nullptr;
     uint64_t *tp_oid = nullptr;
+    // the buffers of the epoch dv_tpcc_epoch_begin took last (dv_tpcc_epoch_carry's stale check)
+    const uint64_t *tp_last_keys = nullptr, *tp_last_args = nullptr;
 
     // workspace (capacities from cfg)
     uint64_t *pairs[2] = {nullptr, nullptr};
@@ -879,6 +881,28 @@ int carry_bufs(dv_ctx *c, uint32_t nb) {
     c->carry_nb = nb ? nb : 1;
     return DV_OK;
 }
+
+// the decided epoch's aborted txns into `out` (checked by the callers), the
+// operation words of a TPC-C epoch (args) into out_args; reads the totals back
+int carry_decided(dv_ctx *c, const dv_epoch_dev *ep, uint32_t max_txn, dv_epoch_dev *out, const uint64_t *args,
+                  uint64_t *out_args) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int r = carry_bufs(c, carry_blocks(ep->n_txn));
+    if (r) return r;
+    launch_carry(c->stream, c->status, c->rs, c->re, ep->n_txn, max_txn, ep->keys, ep->types,
+                 ep->tables, const_cast<uint64_t *>(out->keys), const_cast<uint8_t *>(out->types),
+                 const_cast<uint32_t *>(out->acc_txn),
+                 ep->tables ? const_cast<uint8_t *>(out->tables) : nullptr,
+                 c->carry_b, c->carry_b + c->carry_nb, c->carry_tot, args, out_args);
+    HIPCHK(hipGetLastError());
+    uint32_t tot[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(tot, c->carry_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out->n_txn = tot[0];
+    out->n_acc = tot[1];
+    out->max_txn_acc = ep->max_txn_acc;
+    return DV_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -890,23 +914,23 @@ int dv_epoch_carry(dv_ctx *c, const dv_epoch_dev *ep, uint32_t max_txn, dv_epoch
     if (ep->n_txn != c->n_txn || ep->n_acc != c->n_acc) return DV_ERR_STATE;  // not the last epoch
     if (ep->n_acc && (!out->keys || !out->types || !out->acc_txn || (ep->tables && !out->tables)))
         return DV_ERR_ARG;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const uint32_t nb = carry_blocks(ep->n_txn);
-    int r = carry_bufs(c, nb);
-    if (r) return r;
-    launch_carry(c->stream, c->status, c->rs, c->re, ep->n_txn, max_txn, ep->keys, ep->types,
-                 ep->tables, const_cast<uint64_t *>(out->keys), const_cast<uint8_t *>(out->types),
-                 const_cast<uint32_t *>(out->acc_txn),
-                 ep->tables ? const_cast<uint8_t *>(out->tables) : nullptr,
-                 c->carry_b, c->carry_b + c->carry_nb, c->carry_tot);
-    HIPCHK(hipGetLastError());
-    uint32_t tot[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(tot, c->carry_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    out->n_txn = tot[0];
-    out->n_acc = tot[1];
-    out->max_txn_acc = ep->max_txn_acc;
-    return DV_OK;
+    return carry_decided(c, ep, max_txn, out, nullptr, nullptr);
+}
+
+// dv_epoch_carry for the TPC-C epoch decided last: the carried accesses'
+// operation words travel with them (k_carry_copy<true>)
+int dv_tpcc_epoch_carry(dv_ctx *c, const dv_epoch_dev *ep, const uint64_t *d_args, uint32_t max_txn,
+                        dv_epoch_dev *out, uint64_t *out_args) {
+    KProfScope kps_(c);
+    if (!c || !ep || !out || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
+    if (ep->n_acc && (!ep->keys || !ep->types || !ep->tables || !d_args || !out->keys || !out->types ||
+                      !out->acc_txn || !out->tables || !out_args))
+        return DV_ERR_ARG;
+    if (c->phase != 0 || c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
+    if (ep->n_txn != c->n_txn || ep->n_acc != c->n_acc || ep->keys != c->tp_last_keys ||
+        d_args != c->tp_last_args)
+        return DV_ERR_STATE;  // not the last epoch
+    return carry_decided(c, ep, max_txn, out, d_args, out_args);
 }
 
 int dv_epoch_group_carry(dv_ctx *c, const dv_epoch_dev *homes, uint32_t n_homes, uint32_t txns_per_rank,
@@ -1423,8 +1447,10 @@ int epoch_setup(dv_ctx *c, const dv_epoch_dev *ep) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const bool calvin = c->cfg.cc_alg == DV_CALVIN;
     if (ep->n_txn > kMaxTxn || ep->max_txn_acc > kMaxPos) return DV_ERR_ARG;
-    // a device-side access count: single-GPU YCSB, decision rounds (dvcc.h)
-    if (ep->n_acc_dev && (calvin || c->cfg.workload != DV_YCSB || c->rep_P)) return DV_ERR_ARG;
+    // a device-side access count: single GPU, decision rounds (dvcc.h) -- YCSB, or a
+    // TPC-C context without a communicator (its execution bounds by the same word)
+    if (ep->n_acc_dev && (calvin || c->rep_P || (c->cfg.workload != DV_YCSB && (c->cfg.workload != DV_TPCC || c->comm))))
+        return DV_ERR_ARG;
     // verdict-byte stride: 1 << slog >= the longest txn (16 at least)
     uint32_t slog = 7;
     if (!calvin) {
@@ -1665,6 +1691,7 @@ void enqueue_exec(dv_ctx *c, uint8_t *d_commit, bool prologue_done = false) {
         TpccExec x{};
         x.pairs = c->pairs[c->sorted];
         x.n = c->n_acc;
+        x.n_dev = c->n_acc_is_bound ? c->r0_n_dev : nullptr;  // (dv_epoch_begin: the epoch's n_acc_dev)
         x.status = c->status;
         x.tb_start = c->tb_start;
         x.args = c->tp_args;
@@ -3165,6 +3192,72 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     return DV_OK;
 }
 
+// The TPC-C closed loop: one epoch at a time -- decided (a halted decision is
+// finished synchronously inside dv_tpcc_epoch_run_device), then its refill
+// queued behind its execution, so nothing of an epoch's contents or size is
+// read back between epochs.  Not pipelined: epoch k's outcome (its counters)
+// is read before epoch k + 1 is queued.  The refill carries the operation
+// words beside the keys / types / tables / txn ids form (TPC-C has tables and
+// keys above 2^31: no tb form).
+int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint64_t *pool_args,
+                                  const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_txn, dv_epoch_dev *bufs,
+                                  uint64_t *const *buf_args, uint64_t buf_cap, uint32_t n_epochs, int resume,
+                                  uint8_t *const *d_commits, uint64_t *const *d_oids, dv_stats *sts) {
+    KProfScope kps_(c);
+    if (!c || !pool || !pool_args || !pool_begin || !cursor || !bufs || !buf_args || !n_txn ||
+        c->cfg.workload != DV_TPCC)
+        return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    if (c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
+    const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
+    if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
+        bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn || !pool->tables)
+        return DV_ERR_ARG;
+    for (int b = 0; b < 2; b++)
+        if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].tables || !bufs[b].n_acc_dev ||
+            !buf_args[b])
+            return DV_ERR_ARG;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int r = carry_bufs(c, carry_blocks(n_txn));
+    if (r) return r;
+    // epoch k's descriptor: buffer k & 1, its access count on the device
+    auto desc = [&](uint32_t k) {
+        dv_epoch_dev d = bufs[k & 1];
+        d.txn_begin = d.recs32 = nullptr;
+        d.n_txn = n_txn;
+        d.n_acc = bound;
+        d.max_txn_acc = pool->max_txn_acc;
+        d.ts = nullptr;  // (sequence order: carried txns first keep their priority)
+        return d;
+    };
+    // prev's aborted txns (NULL: none), then fresh pool txns, into buffer `into`
+    auto refill = [&](const dv_epoch_dev *prev, const uint64_t *prev_args, int into) {
+        const dv_epoch_dev &o = bufs[into];
+        launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u, prev ? prev->keys : nullptr,
+                      prev ? prev->types : nullptr, prev ? prev->tables : nullptr, pool->keys, pool->types,
+                      pool->tables, pool->acc_txn, pool_begin, pool->n_txn, cursor, n_txn, bound,
+                      const_cast<uint64_t *>(o.keys), const_cast<uint8_t *>(o.types),
+                      const_cast<uint32_t *>(o.acc_txn), const_cast<uint8_t *>(o.tables),
+                      const_cast<uint32_t *>(o.n_acc_dev), c->carry_b, c->carry_b + c->carry_nb, c->carry_tot,
+                      prev ? c->ctr : nullptr, nullptr, nullptr, nullptr, nullptr, prev_args, pool_args,
+                      buf_args[into]);
+        return hip_fail(hipGetLastError(), "refill");
+    };
+    if (!resume) r = refill(nullptr, nullptr, 0);
+    for (uint32_t k = 0; !r && k < n_epochs; k++) {
+        const dv_epoch_dev d = desc(k);
+        r = dv_tpcc_epoch_run_device(c, &d, buf_args[k & 1], d_commits ? d_commits[k] : nullptr,
+                                     d_oids ? d_oids[k] : nullptr, sts ? &sts[k] : nullptr);
+        if (!r) r = refill(&d, buf_args[k & 1], (int)((k + 1) & 1));
+    }
+    if (r) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
+    return DV_OK;
+}
+
 // The closed loop over decision lanes: epoch k on lanes[k % L]; each lane
 // keeps its own pair of epoch buffers (bufs[2l], bufs[2l + 1]) and its epochs
 // form a closed loop of their own -- epoch k + L is epoch k's aborted txns,
@@ -3312,6 +3405,8 @@ int dv_tpcc_epoch_begin(dv_ctx *c, const dv_epoch_dev *ep, const uint64_t *d_arg
     // reports as DV_ERR_KEY_NOT_FOUND
     static const uint64_t kNoArgs = 0;
     c->tp_args = d_args ? d_args : &kNoArgs;  // an empty partition still finishes
+    c->tp_last_keys = ep->keys;
+    c->tp_last_args = d_args;
     c->tp_oid = d_oid;
     c->tp_resolve = true;
     r = dv_epoch_begin(c, ep, nullptr);

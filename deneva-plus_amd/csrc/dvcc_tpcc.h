@@ -8,6 +8,8 @@ namespace dvcc {
 struct TpccExec {
     const uint64_t *pairs;     // row-sorted pairs of the epoch
     uint64_t n;                // accesses
+    const uint32_t *n_dev;     // (device, may be null) their real count when n is only a bound
+                               // (dv_epoch_dev::n_acc_dev; never CALVIN)
     const uint8_t *status;     // per txn
     const uint32_t *tb_start;  // per txn: first access
     const uint64_t *args;      // per access: op << 56 | operand

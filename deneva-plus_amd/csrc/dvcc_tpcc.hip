@@ -65,8 +65,10 @@ __global__ __launch_bounds__(kBlock) void k_tpcc_apply(const uint64_t *__restric
                                                        int oid_direct, uint64_t *__restrict__ oid,
                                                        uint64_t *__restrict__ dsnap, uint64_t dist_base,
                                                        uint64_t dist_rows, Counters *ctr, uint32_t n_txn,
-                                                       uint8_t *__restrict__ commit_out) {
+                                                       uint8_t *__restrict__ commit_out,
+                                                       const uint32_t *__restrict__ n_dev) {
     if (ctr->halt) return;  // rounds not finished
+    if (n_dev && (uint64_t)*n_dev < n) n = *n_dev;  // (the real count of a device-built epoch: the sort's too)
     const uint32_t lane = threadIdx.x & 63;
     {  // the commit bytes and the committed count (k_commit_out's work, one launch fewer)
         uint32_t cc = commit_bytes_grid(status, n_txn, commit_out);
@@ -213,7 +215,7 @@ void launch_tpcc_exec(hipStream_t s, const TpccExec &x) {
     }
     const uint64_t g = std::max<uint64_t>(x.n, (x.n_txn + 15u) / 16u);
     DV_LAUNCH(k_tpcc_apply, grid_for(g), kBlock, 0, s, x.pairs, x.n, x.status, x.tb_start, x.args, x.cols,
-              x.oid_direct ? 1 : 0, x.oid, x.dsnap, x.dist_base, x.dist_rows, x.ctr, x.n_txn, x.commit_out);
+              x.oid_direct ? 1 : 0, x.oid, x.dsnap, x.dist_base, x.dist_rows, x.ctr, x.n_txn, x.commit_out, x.n_dev);
     if (x.oid_direct) return;
     if (!x.dist_rows) return;
     const uint32_t blocks = (uint32_t)((x.dist_rows + kBlock / 64 - 1) / (kBlock / 64));  // (a wave per district)

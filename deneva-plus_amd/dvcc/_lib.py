@@ -210,6 +210,10 @@ SIGNATURES = [
     ("dv_tpcc_epoch_run_device", ctypes.c_int, [_vp, _P(EpochDev), _vp, _vp, _vp, _P(Stats)]),
     ("dv_tpcc_epoch_run_device_batch", ctypes.c_int, [_vp, _P(EpochDev), _vp, ctypes.c_uint32, _vp, _vp,
                                                       _P(Stats)]),
+    ("dv_tpcc_epoch_carry", ctypes.c_int, [_vp, _P(EpochDev), _vp, ctypes.c_uint32, _P(EpochDev), _vp]),
+    ("dv_tpcc_epoch_run_closed_loop", ctypes.c_int,
+     [_vp, _P(EpochDev), _vp, _vp, _vp, ctypes.c_uint32, _P(EpochDev), _P(_vp), ctypes.c_uint64, ctypes.c_uint32,
+      ctypes.c_int, _P(_vp), _P(_vp), _P(Stats)]),
     ("dv_comm_set_mode", ctypes.c_int, [_vp, ctypes.c_int]),
     ("dv_epoch_run_device_batch", ctypes.c_int, [_vp, _P(EpochDev), ctypes.c_uint32, _P(_vp), _P(Stats)]),
     ("dv_open_lane", ctypes.c_int, [_vp, _P(_vp)]),

@@ -157,10 +157,11 @@ class DeviceEpoch:
         ts = getattr(self, "ts", None)
         tb = getattr(self, "txn_begin", None)
         r32 = getattr(self, "recs32", None)
+        nd = getattr(self, "n_acc_dev", None)  # (device word: n_acc is then only a bound, dv_epoch_dev)
         d = L.EpochDev(self.keys.data_ptr(), self.types.data_ptr(), self.acc_txn.data_ptr(),
                        self.tables.data_ptr() if self.tables is not None else None,
                        self.n_acc, self.n_txn, self.max_txn_acc, ts.data_ptr() if ts is not None else None,
-                       None, tb.data_ptr() if tb is not None else None, r32.data_ptr() if r32 is not None else None)
+                       nd.data_ptr() if nd is not None else None, tb.data_ptr() if tb is not None else None, r32.data_ptr() if r32 is not None else None)
         self._desc_memo = (self._ver, d, bytes(d))
         return d
 

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .engine import CCEngine, DeviceEpoch, Epoch, _ptr
+from .engine import CCEngine, ClosedLoopBufs, DeviceEpoch, Epoch, _commit_ptrs, _ptr
 
 TABLES = {"WAREHOUSE": L.T_WAREHOUSE, "DISTRICT": L.T_DISTRICT, "CUSTOMER": L.T_CUSTOMER,
           "ITEM": L.T_ITEM, "STOCK": L.T_STOCK, "CUST_LAST": L.T_CUST_LAST}
@@ -62,6 +62,26 @@ def gen(p, n_txn, seed, home_part=0):
     n = int(tb[-1])
     return TpccEpoch(keys[:n].copy(), types[:n].copy(), tb, tables[:n].copy(), args[:n].copy(), tt,
                      own[:n].copy())
+
+
+class TpccLoopBufs(ClosedLoopBufs):
+    """The TPC-C closed loop's two epoch buffers (dv_tpcc_epoch_run_closed_loop):
+    ClosedLoopBufs with table bytes (never the tb form), and the operation
+    words of each buffer's accesses."""
+
+    def __init__(self, cap, device):
+        import torch
+        super().__init__(cap, True, device)
+        self.args = [torch.empty(max(1, self.cap), dtype=torch.int64, device=device) for _ in range(2)]
+
+    def swap(self):
+        super().swap()
+        self.args.reverse()
+
+    def epoch(self, b, n_txn, max_txn_acc):
+        """buffer b's epoch as (DeviceEpoch, args) (reads its access count)"""
+        dep = super().epoch(b, n_txn, max_txn_acc)
+        return dep, self.args[b][:dep.n_acc]
 
 
 class TpccEngine(CCEngine):
@@ -127,6 +147,57 @@ class TpccEngine(CCEngine):
             L.check(L.lib().dv_tpcc_epoch_run_device_batch(self._ctx, descs, args, n, ptrs(d_commits),
                                                            ptrs(d_oids), sts), "dv_tpcc_epoch_run_device_batch")
         return list(sts)
+
+    def carry(self, dep, d_args, max_txn=None):
+        """Abort carry-over (dv_tpcc_epoch_carry): the last epoch's (`dep`'s,
+        with operation words d_args) aborted txns, in sequence order, at most
+        max_txn of them, as (DeviceEpoch, args)."""
+        import torch
+        dev = dep.keys.device
+        n = max(1, dep.n_acc)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        types = torch.empty(n, dtype=torch.uint8, device=dev)
+        txn = torch.empty(n, dtype=torch.int32, device=dev)
+        tabs = torch.empty(n, dtype=torch.uint8, device=dev)
+        args = torch.empty(n, dtype=torch.int64, device=dev)
+        out = L.EpochDev(keys.data_ptr(), types.data_ptr(), txn.data_ptr(), tabs.data_ptr(), 0, 0, 0)
+        cap = dep.n_txn if max_txn is None else max_txn
+        self._after_torch()
+        L.check(L.lib().dv_tpcc_epoch_carry(self._ctx, ctypes.byref(dep.desc()), _ptr(d_args), cap,
+                                            ctypes.byref(out), _ptr(args)), "dv_tpcc_epoch_carry")
+        n = int(out.n_acc)
+        return (DeviceEpoch.from_tensors(keys[:n], types[:n], txn[:n], int(out.n_txn), tables=tabs[:n],
+                                         max_txn_acc=int(out.max_txn_acc)), args[:n])
+
+    def closed_loop(self, pool, pool_args, pool_begin, n_txn, n_epochs, cursor=None, bufs=None, d_commits=None,
+                    d_oids=None, resume=False):
+        """The TPC-C closed loop on the device (dv_tpcc_epoch_run_closed_loop):
+        n_epochs epochs of n_txn txns, each the previous one's aborted txns
+        (with their operation words) then fresh ones from `pool` (a DeviceEpoch
+        with tables and max_txn_acc > 0; pool_args: its operation words;
+        pool_begin: its n_txn + 1 access offsets, int32 device tensor) from the
+        device word `cursor` (int32 tensor, advanced).  bufs: TpccLoopBufs
+        (allocated when None); d_commits / d_oids: a device tensor per epoch,
+        one for all, or None.  Returns (stats list, bufs, cursor); the next
+        epoch is in bufs.epoch(n_epochs & 1)."""
+        import torch
+        dev = pool.keys.device
+        if cursor is None:
+            cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        if bufs is None:
+            bufs = TpccLoopBufs(n_txn * pool.max_txn_acc, dev)
+        arr = (L.EpochDev * 2)(*[bufs.desc(b) for b in range(2)])
+        bargs = getattr(bufs, "args", None) or [None, None]
+        aps = (ctypes.c_void_p * 2)(*[(int(t.data_ptr()) if t is not None else None) for t in bargs])
+        n = max(1, n_epochs)
+        sts = (L.Stats * n)()
+        self._after_torch()
+        L.check(L.lib().dv_tpcc_epoch_run_closed_loop(self._ctx, ctypes.byref(pool.desc()), _ptr(pool_args),
+                                                      _ptr(pool_begin), _ptr(cursor), n_txn, arr, aps, bufs.cap,
+                                                      n_epochs, int(resume), _commit_ptrs(d_commits, n),
+                                                      _commit_ptrs(d_oids, n), sts),
+                "dv_tpcc_epoch_run_closed_loop")
+        return list(sts)[:n_epochs], bufs, cursor
 
     def run_tpcc_epoch_part(self, home, d_args, d_owner, txns_per_rank, d_commit, d_oid=None):
         """Config E from the engine (dv_tpcc_epoch_run_part): this rank's

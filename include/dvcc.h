@@ -179,9 +179,13 @@ typedef struct dv_epoch_dev {
                                 NULL only (DV_ERR_ARG voted on every rank). */
     const uint32_t *n_acc_dev; /* (device) the real access count when it is
                                 known only on the device (dv_epoch_refill):
-                                n_acc is then an upper bound.  NULL: n_acc is
-                                exact.  Single-GPU YCSB entry points, NO_WAIT /
-                                WAIT_DIE / OCC (DV_ERR_ARG otherwise). */
+                                n_acc is then an upper bound, and arrays may
+                                hold anything past the real count.  NULL: n_acc
+                                is exact.  Single-GPU entry points, NO_WAIT /
+                                WAIT_DIE / OCC: the YCSB ones, and
+                                dv_tpcc_epoch_run_device / dv_tpcc_epoch_begin
+                                on a context without a communicator
+                                (DV_ERR_ARG otherwise). */
     const uint32_t *txn_begin; /* (device, optional) [n_txn + 1] the same epoch's
                                 txn boundaries -- txn t's accesses are
                                 [txn_begin[t], txn_begin[t + 1]), from 0 to
@@ -707,6 +711,44 @@ int dv_tpcc_epoch_run_device(dv_ctx *ctx, const dv_epoch_dev *ep, const uint64_t
 int dv_tpcc_epoch_run_device_batch(dv_ctx *ctx, const dv_epoch_dev *eps, const uint64_t *const *d_args,
                                    uint32_t n, uint8_t *const *d_commits, uint64_t *const *d_oids,
                                    dv_stats *sts);
+
+/* dv_epoch_carry for TPC-C: after dv_tpcc_epoch_run_device (or
+ * dv_tpcc_epoch_begin ... dv_epoch_finish) of `ep` with operation words
+ * d_args -- the epoch the context decided last, single GPU, not CALVIN, no
+ * communicator (DV_ERR_STATE otherwise; a context that is not DV_TPCC, or a
+ * missing buffer: DV_ERR_ARG) -- writes the accesses of its aborted txns, in
+ * sequence order and renumbered 0..C-1, C = min(aborted, max_txn), into
+ * out->keys / types / acc_txn / tables and their operation words into
+ * out_args: device arrays with room for ep->n_acc accesses (ep->tables is
+ * required).  Sets out->n_txn = C, out->n_acc, out->max_txn_acc.  The query
+ * is carried unchanged: a Payment by last name is looked up again. */
+int dv_tpcc_epoch_carry(dv_ctx *ctx, const dv_epoch_dev *ep, const uint64_t *d_args, uint32_t max_txn,
+                        dv_epoch_dev *out, uint64_t *out_args);
+
+/* dv_epoch_run_closed_loop for TPC-C (NO_WAIT / WAIT_DIE / OCC, single GPU,
+ * no communicator; CALVIN or a communicator: DV_ERR_STATE; a context that is
+ * not DV_TPCC: DV_ERR_ARG): n_epochs epochs of n_txn txns, epoch k + 1 being
+ * epoch k's aborted txns -- in sequence order, renumbered from 0, with their
+ * operation words -- then fresh txns taken in order from `pool` (tables
+ * required; pool_args: its operation words; pool_begin: pool->n_txn + 1
+ * access offsets) starting at *cursor, wrapping.  Each next epoch is built on
+ * the device behind epoch k's execution, its access count left in
+ * bufs[].n_acc_dev; the host reads back nothing of an epoch's contents or
+ * size.  bufs[2] / buf_args[2]: the epochs' device buffers (keys / types /
+ * acc_txn / tables and operation words, buf_cap accesses each; n_acc_dev: a
+ * device word); epoch k lives in buffer k & 1.  Argument checks, resume and
+ * the buffer parity on return as dv_epoch_run_closed_loop.  d_commits /
+ * d_oids / sts: NULL or n_epochs entries (entries may be NULL); d_oids[k]
+ * receives the committed NewOrders' o_id as dv_tpcc_epoch_run_device writes
+ * it.  Epochs run one at a time (epoch k's counters are read before epoch
+ * k + 1 is queued); a halted epoch is decided again synchronously before its
+ * successor is rebuilt.  The epochs are exactly those of a host loop of
+ * dv_tpcc_epoch_run_device + dv_tpcc_epoch_carry + the fresh txns
+ * (tests/test_tpcc_closed_loop.py). */
+int dv_tpcc_epoch_run_closed_loop(dv_ctx *ctx, const dv_epoch_dev *pool, const uint64_t *pool_args,
+                                  const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_txn, dv_epoch_dev *bufs,
+                                  uint64_t *const *buf_args, uint64_t buf_cap, uint32_t n_epochs, int resume,
+                                  uint8_t *const *d_commits, uint64_t *const *d_oids, dv_stats *sts);
 
 /* TPC-C epochs over decision lanes (dv_open_lane on a DV_TPCC context), as
  * dv_epoch_run_device_lanes: epoch k decided on lanes[k % n_lanes], executions
