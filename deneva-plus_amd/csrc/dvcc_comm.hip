@@ -693,8 +693,9 @@ __device__ __forceinline__ uint64_t match_owner(uint32_t o, uint64_t valid, uint
 template <class Emit>
 __device__ __forceinline__ void walk_committed_txns(const uint32_t *__restrict__ tb_start,
                                                     const uint32_t *__restrict__ tb_end,
-                                                    const uint32_t *__restrict__ acc_row, uint32_t n_txn,
-                                                    const uint8_t *__restrict__ status, Emit &emit) {
+                                                    const uint32_t *__restrict__ acc_row, const RecRows &rr,
+                                                    uint32_t n_txn, const uint8_t *__restrict__ status,
+                                                    Emit &emit) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t step = gridDim.x * (kBlock / 64) * 64;
     for (uint32_t base = (blockIdx.x * (kBlock / 64) + wave) * 64; base < n_txn; base += step) {
@@ -721,7 +722,7 @@ __device__ __forceinline__ void walk_committed_txns(const uint32_t *__restrict__
             }
             const uint32_t sa0 = __shfl(a0, (int)src, 64), spre = __shfl(pre, (int)src, 64);
             const bool v = g < total;
-            const uint32_t ar = v ? acc_row[sa0 + (g - spre)] : 0u;
+            const uint32_t ar = v ? row_word(acc_row, rr, sa0 + (g - spre)) : 0u;
             emit(v, ar & ~AR_WR, (ar & AR_WR) ? RT_WR : 0u, base + src);
         }
     }
@@ -753,9 +754,10 @@ struct RouteSrc {
     const uint8_t *ew;
     uint64_t n;
     const uint8_t *status;
+    RecRows rr;  // (SRC 0: the row words from the epoch's records instead of acc_row)
     template <class Emit>
     __device__ void walk(Emit &emit) const {
-        if (SRC == 0) walk_committed_txns(tb_start, tb_end, acc_row, n_txn, status, emit);
+        if (SRC == 0) walk_committed_txns(tb_start, tb_end, acc_row, rr, n_txn, status, emit);
         else walk_row_queues(pairs, el, ew, n, status, emit);
     }
 };
@@ -979,9 +981,9 @@ __global__ void k_route_words(const uint32_t *__restrict__ tot, uint32_t P, uint
 }
 
 void launch_route_txn(hipStream_t s, const RouteOut &ro, const uint32_t *tb_start, const uint32_t *tb_end,
-                      const uint32_t *acc_row, uint32_t n_txn, const uint8_t *status, Counters *ctr,
-                      uint8_t *d_commit) {
-    const RouteSrc<0> src{tb_start, tb_end, acc_row, n_txn, nullptr, nullptr, nullptr, 0, status};
+                      const uint32_t *acc_row, const RecRows &rr, uint32_t n_txn, const uint8_t *status,
+                      Counters *ctr, uint8_t *d_commit) {
+    const RouteSrc<0> src{tb_start, tb_end, acc_row, n_txn, nullptr, nullptr, nullptr, 0, status, rr};
     DV_LAUNCH((k_route_count<0>), kRouteBlocks, kBlock, 0, s, src, ro, ctr, d_commit);
     DV_LAUNCH(k_route_scan, ro.P, kBlock, 0, s, ro);
     if (ro.wrote) *ro.wrote = ro.orec != nullptr;
@@ -990,7 +992,7 @@ void launch_route_txn(hipStream_t s, const RouteOut &ro, const uint32_t *tb_star
 
 void launch_route_rowq(hipStream_t s, const RouteOut &ro, const uint64_t *pairs, const uint64_t *el,
                        const uint8_t *ew, uint64_t n, const uint8_t *status, Counters *ctr) {
-    const RouteSrc<1> src{nullptr, nullptr, nullptr, 0, pairs, el, ew, n, status};
+    const RouteSrc<1> src{nullptr, nullptr, nullptr, 0, pairs, el, ew, n, status, RecRows{}};
     DV_LAUNCH((k_route_count<1>), kRouteBlocks, kBlock, 0, s, src, ro, ctr, (uint8_t *)nullptr);
     RouteOut r0 = ro;  // (CALVIN's commit count comes after the route: k_route_words writes the record)
     r0.orec = nullptr;

@@ -363,4 +363,18 @@ __device__ __forceinline__ bool kk_row(const KillKeys &kk, uint64_t key, uint64_
     }
 }
 
+// the row word (row | AR_WR) of access a: the probe's acc_row word or, in a
+// RecRows epoch, the access's own record with dense_base applied.  No check
+// and no error here: the keys of the prefix's accesses were validated by
+// k_probe_tb and those of the later ones by k_kill, and a rejected epoch
+// (input_err) reads no row word at all.  (One load path for both 4-byte
+// sources, the choice uniform: a caller's unrolled row-word loads stay in
+// flight together as they were with acc_row alone.)
+__device__ __forceinline__ uint32_t row_word(const uint32_t *__restrict__ acc_row, const RecRows &rr, uint64_t a) {
+    if (rr.on && !rr.recs)
+        return (uint32_t)(rr.keys[a] + rr.dense_base) | (rr.types[a] == DV_WR ? AR_WR : 0u);
+    const uint32_t w = (rr.on ? rr.recs : acc_row)[a];
+    return ((w & ~AR_WR) + (rr.on ? (uint32_t)rr.dense_base : 0u)) | (w & AR_WR);
+}
+
 }  // namespace dvcc

@@ -507,11 +507,25 @@ struct RouteOut {
     bool *wrote = nullptr;
     bool defer = false;                    // the decider's counter read waits for the outcome vote
 };
-// NO_WAIT / WAIT_DIE / OCC: the committed txns' accesses (txn-major acc_row),
-// and the commit bytes and count in the same pass (k_commit_out's work)
+// A prefix-kill epoch with its txn boundaries on a dense map (KillKeys with
+// dense_lim, below) keeps no acc_row copy of its accesses: the row word of
+// access a is its own record with dense_base applied (row_word, dvcc_common.h),
+// which k_kill computes anyway -- so k_prefix_mark, k_exec_txn and the route
+// walk, which read the committed txns' row words only (~2 % of a config-D
+// epoch), take them from the records.  The part of KillKeys those kernels
+// need (not its table descriptors); on = false: acc_row holds the row words.
+struct RecRows {
+    const uint32_t *recs;
+    const uint64_t *keys;
+    const uint8_t *types;
+    uint64_t dense_base;
+    bool on;
+};
+// NO_WAIT / WAIT_DIE / OCC: the committed txns' accesses (txn-major acc_row,
+// or rr), and the commit bytes and count in the same pass (k_commit_out's work)
 void launch_route_txn(hipStream_t s, const RouteOut &ro, const uint32_t *tb_start, const uint32_t *tb_end,
-                      const uint32_t *acc_row, uint32_t n_txn, const uint8_t *status, Counters *ctr,
-                      uint8_t *d_commit);
+                      const uint32_t *acc_row, const RecRows &rr, uint32_t n_txn, const uint8_t *status,
+                      Counters *ctr, uint8_t *d_commit);
 // CALVIN: every access, in row order (sorted pairs, queue elements, "an
 // earlier write precedes" flags)
 void launch_route_rowq(hipStream_t s, const RouteOut &ro, const uint64_t *pairs, const uint64_t *el,
@@ -608,8 +622,8 @@ uint64_t row_state_words(uint64_t rows);
 // finalize): the prefix's statuses are read from its fact words and written
 // to status
 void launch_prefix_mark(hipStream_t s, uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                        const uint32_t *acc_row, uint32_t K, uint32_t *row_state, uint64_t rs_words, int nowait,
-                        Counters *ctr, const uint32_t *words);
+                        const uint32_t *acc_row, const RecRows &rr, uint32_t K, uint32_t *row_state,
+                        uint64_t rs_words, int nowait, Counters *ctr, const uint32_t *words);
 uint32_t kill_tiles(uint32_t n_after);  // look-back tiles of k_kill_compact (descriptors per array)
 // k_kill (every access after the prefix's against the row state, one bit
 // per access into kill_bits[kill_words(n_acc)]; NO_WAIT / WAIT_DIE, skip_bits
@@ -619,8 +633,9 @@ uint32_t kill_tiles(uint32_t n_after);  // look-back tiles of k_kill_compact (de
 uint64_t kill_words(uint64_t n_acc);
 // kk (an epoch with its txn boundaries, launch_probe_tb): the accesses after
 // the prefix were not probed -- k_kill probes their keys itself (a missing key:
-// ERRB_KEY, the epoch rejected) and k_kill_emit the survivors' (their acc_row
-// words, for the execution, and their sort keys)
+// ERRB_KEY, the epoch rejected) and k_kill_emit the survivors' (their sort
+// keys and, unless the map is dense (RecRows), their acc_row words for the
+// execution)
 struct KillKeys {
     Tables tabs;
     const uint64_t *keys;
@@ -653,6 +668,11 @@ __device__ __forceinline__ uint64_t kk_key(const KillKeys &kk, uint64_t a, uint3
     }
     wr = kk.types[a] == DV_WR ? 1u : 0u;
     return kk.keys[a];
+}
+// its RecRows (dense map), or none: acc_row holds the row words
+inline RecRows rec_rows(const KillKeys *kk) {
+    if (!kk || !kk->dense_lim) return RecRows{nullptr, nullptr, nullptr, 0, false};
+    return RecRows{kk->recs, kk->keys, kk->types, kk->dense_base, true};
 }
 // (n_acc_dev: the epoch's real access count when n_acc is a bound, else null)
 void launch_kill_compact(hipStream_t s, const uint32_t *tb_start, const uint32_t *tb_end, const uint32_t *acc_row,
@@ -699,8 +719,8 @@ void launch_exec(hipStream_t s, const uint64_t *pairs, const uint64_t *el, const
 // map whose row r holds key r - pk_base (k_ycsb_load), so a read's primary
 // key comes from its row instead of a second random line of the pkey column
 void launch_exec_txn(hipStream_t s, const uint32_t *tb_start, const uint32_t *tb_end,
-                     const uint32_t *acc_row, uint32_t n_txn, const uint8_t *status, uint64_t *f0,
-                     const uint64_t *pkey, bool fused, Counters *ctr, RowMap rm, uint8_t *d_commit,
+                     const uint32_t *acc_row, const RecRows &rr, uint32_t n_txn, const uint8_t *status,
+                     uint64_t *f0, const uint64_t *pkey, bool fused, Counters *ctr, RowMap rm, uint8_t *d_commit,
                      bool pk_dense = false, uint64_t pk_base = 0);
 void launch_commit_out(hipStream_t s, const uint8_t *status, uint32_t n_txn, uint8_t *d_commit,
                        Counters *ctr);

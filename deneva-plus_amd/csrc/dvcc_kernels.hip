@@ -370,7 +370,8 @@ void launch_probe(hipStream_t s, const Tables &tabs, const uint64_t *keys, const
 // each txn's range is [txn_begin[t], txn_begin[t + 1]) for every later kernel
 // -- so this launch touches only what the prefix's decision needs: a thread
 // per prefix txn (t < K) probes its accesses (IndexHash::index_read,
-// index_hash.cpp:137-153) into acc_row and the prefix's sort keys, and every
+// index_hash.cpp:137-153) into the prefix's sort keys and acc_row (null on a
+// dense map, whose row words are read from the records: RecRows), and every
 // txn's boundaries are checked (ascending from 0 to n_acc: else ERRB_TXN; a
 // txn longer than 1 << slog: ERRB_BIG; WAIT_DIE timestamps rising: else
 // ERRB_TS).  The accesses after the prefix are probed by the kill pass
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_tb(Tables tabs, const uint64_t
                 probe_row(tabs.t[0], tabs.n > 0, key[j], row, ctr);
                 const uint32_t wr = wrs[j];
                 const uint32_t pos = j0 + j;
-                acc_row[a0 + pos] = (uint32_t)row | (wr ? AR_WR : 0u);
+                if (acc_row) acc_row[a0 + pos] = (uint32_t)row | (wr ? AR_WR : 0u);
                 pairs[a0 + pos] = pair_pack(row, t, (pos >> slog) ? 0u : pos, wr);
             }
         }
@@ -1474,8 +1475,8 @@ void launch_exec(hipStream_t s, const uint64_t *pairs, const uint64_t *el, const
 }
 
 // NO_WAIT / WAIT_DIE / OCC: run_ycsb_1 for the committed txns only (acc_row
-// from the probe).  A committed reader never sees a committed writer's value
-// here (2PL: the two conflict, so one launch does both; OCC: reads happen in
+// from the probe, or the epoch's own records: RecRows).  A committed reader
+// never sees a committed writer's value here (2PL: the two conflict, so one launch does both; OCC: reads happen in
 // the access phase, occ.cpp:116-294, so the reads run in a launch before the
 // writes).  Each wave takes 64 consecutive txns and spreads the accesses of
 // its committed ones over its lanes (a prefix sum of their lengths): at a
@@ -1488,7 +1489,7 @@ enum : int { EX_READS = 1, EX_WRITES = 2, EX_COMMIT = 4 };
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_exec_txn(const uint32_t *__restrict__ tb_start,
                                                      const uint32_t *__restrict__ tb_end,
-                                                     const uint32_t *__restrict__ acc_row,
+                                                     const uint32_t *__restrict__ acc_row, RecRows rr,
                                                      uint32_t n_txn,
                                                      const uint8_t *__restrict__ status,
                                                      uint64_t *__restrict__ f0,
@@ -1535,7 +1536,7 @@ __global__ __launch_bounds__(kBlock) void k_exec_txn(const uint32_t *__restrict_
             const uint32_t sa0 = __shfl(a0, (int)src, 64), spre = __shfl(pre, (int)src, 64);
             if (g >= total) continue;
             const uint32_t tt = base + src;
-            const uint32_t ar = acc_row[sa0 + (g - spre)];
+            const uint32_t ar = row_word(acc_row, rr, sa0 + (g - spre));
             uint64_t row = ar & ~AR_WR;
             if (!own_row(rm, row)) continue;  // (replicated epochs: another partition's row)
             if ((MODE & EX_READS) && !(ar & AR_WR))
@@ -1568,20 +1569,20 @@ __global__ __launch_bounds__(kBlock) void k_exec_txn(const uint32_t *__restrict_
 }
 
 void launch_exec_txn(hipStream_t s, const uint32_t *tb_start, const uint32_t *tb_end,
-                     const uint32_t *acc_row, uint32_t n_txn, const uint8_t *status, uint64_t *f0,
-                     const uint64_t *pkey, bool fused, Counters *ctr, RowMap rm, uint8_t *d_commit,
+                     const uint32_t *acc_row, const RecRows &rr, uint32_t n_txn, const uint8_t *status,
+                     uint64_t *f0, const uint64_t *pkey, bool fused, Counters *ctr, RowMap rm, uint8_t *d_commit,
                      bool pk_dense, uint64_t pk_base) {
     const int pkd = pk_dense && rm.P == 0 ? 1 : 0;  // (replicated epochs read the column)
     if (n_txn == 0) return;
     uint32_t blocks = (n_txn + kBlock - 1) / kBlock;
     if (blocks > 4096) blocks = 4096;
     if (fused) {
-        DV_LAUNCH((k_exec_txn<EX_READS | EX_WRITES | EX_COMMIT>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, n_txn,
+        DV_LAUNCH((k_exec_txn<EX_READS | EX_WRITES | EX_COMMIT>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, rr, n_txn,
                                                                               status, f0, pkey, ctr, rm, d_commit, pkd, pk_base);
     } else {
-        DV_LAUNCH((k_exec_txn<EX_READS | EX_COMMIT>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, n_txn, status, f0,
+        DV_LAUNCH((k_exec_txn<EX_READS | EX_COMMIT>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, rr, n_txn, status, f0,
                                                                    pkey, ctr, rm, d_commit, pkd, pk_base);
-        DV_LAUNCH((k_exec_txn<EX_WRITES>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, n_txn, status, f0,
+        DV_LAUNCH((k_exec_txn<EX_WRITES>), blocks, kBlock, 0, s, tb_start, tb_end, acc_row, rr, n_txn, status, f0,
                                                         pkey, ctr, rm, nullptr, pkd, pk_base);
     }
 }

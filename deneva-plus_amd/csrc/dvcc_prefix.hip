@@ -79,7 +79,8 @@ __device__ __forceinline__ uint32_t bloom_bit(uint32_t row) { return (row * 0x9E
 uint64_t row_state_words(uint64_t rows) { return (((rows + 15) / 16 + 3) & ~3ull) + kBloomWords; }
 
 // the rows of the committed prefix txns into the bitmap; lane per txn, its
-// accesses from the probe's txn-major acc_row.  The hot rows [0, kHotRows)
+// accesses from the probe's txn-major acc_row (or the epoch's own records,
+// RecRows).  The hot rows [0, kHotRows)
 // -- which many committed readers share -- are ORed into an LDS copy of
 // their bitmap words first, then each nonzero word into the bitmap with one
 // atomic per block (one device-scope atomic per access on a shared word ran
@@ -91,8 +92,9 @@ constexpr int kMarkBlock = DVCC_MARK_BLOCK;  // (16 KiB of LDS per block)
 __global__ __launch_bounds__(kMarkBlock) void k_prefix_mark(uint8_t *__restrict__ status,
                                                             const uint32_t *__restrict__ tb_start,
                                                             const uint32_t *__restrict__ tb_end,
-                                                            const uint32_t *__restrict__ acc_row, uint32_t K,
-                                                            uint32_t *__restrict__ row_state, uint64_t state_words,
+                                                            const uint32_t *__restrict__ acc_row, RecRows rr,
+                                                            uint32_t K, uint32_t *__restrict__ row_state,
+                                                            uint64_t state_words,
                                                             uint32_t *__restrict__ bloom, int nowait,
                                                             Counters *__restrict__ ctr,
                                                             const uint32_t *__restrict__ words) {
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(kMarkBlock) void k_prefix_mark(uint8_t *__restrict_
         for (uint32_t a0 = tb_start[t], e = tb_end[t]; a0 < e; a0 += kMU) {
             uint32_t arw[kMU];
 #pragma unroll
-            for (uint32_t u = 0; u < kMU; u++) arw[u] = a0 + u < e ? acc_row[a0 + u] : 0u;
+            for (uint32_t u = 0; u < kMU; u++) arw[u] = a0 + u < e ? row_word(acc_row, rr, a0 + u) : 0u;
 #pragma unroll
             for (uint32_t u = 0; u < kMU; u++) {
                 if (a0 + u >= e) continue;
@@ -337,6 +339,16 @@ __device__ __forceinline__ uint32_t range_count(const uint64_t *__restrict__ bit
     return c;
 }
 
+// the bits of accesses [a0, a1), at most 32 of them, as one word (bit j:
+// access a0 + j) -- from at most two words of `bits`
+__device__ __forceinline__ uint32_t range_field(const uint64_t *__restrict__ bits, uint32_t a0, uint32_t a1) {
+    if (a0 >= a1) return 0u;
+    const uint32_t wlo = a0 >> 6, whi = (a1 - 1) >> 6, sh = a0 & 63u, len = a1 - a0;
+    uint64_t f = bits[wlo] >> sh;
+    if (whi != wlo) f |= bits[whi] << (64u - sh);  // (the range crosses a word: sh != 0)
+    return (uint32_t)f & (len >= 32u ? ~0u : (1u << len) - 1u);
+}
+
 // the index of the r-th access from a0 on whose skip bit is clear (the
 // caller knows there is one)
 __device__ __forceinline__ uint32_t nth_kept(const uint64_t *__restrict__ skip, uint32_t a0, uint32_t r) {
@@ -409,8 +421,11 @@ __global__ __launch_bounds__(kBlock) void k_kill_count(const uint32_t *__restric
 }
 
 // KEYS (launch_probe_tb epochs): the survivors' accesses were never probed --
-// their rows come from their keys here: their sort keys, and acc_row for every
-// access of a survivor (the execution's, the skipped reads' included)
+// their rows come from their keys here: their sort keys and, KEYS 1, acc_row
+// for every access of a survivor (the execution's, the skipped reads'
+// included).  KEYS 2 writes no acc_row: the execution reads the row words of
+// the few survivors that commit from the records (RecRows), so only the
+// survivors' kept accesses are touched here.
 template <int KEYS>  // as k_kill
 __global__ __launch_bounds__(kBlock) void k_kill_emit(
     const uint32_t *__restrict__ tb_start, const uint32_t *__restrict__ tb_end, uint32_t *__restrict__ acc_row,
@@ -423,11 +438,12 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
     __shared__ uint32_t s_sub0, s_ab0, s_nsurv, s_nacc, s_nfull;
     __shared__ uint32_t l_a0[kKillTile], l_pre[kKillTile + 1];  // per survivor: first access, access prefix
     __shared__ uint32_t l_st[kKillTile], l_len[kKillTile];      // per tile txn: first access, info word
-    // KEYS: per tile txn its end; per survivor the prefix of its whole length
-    // and its skipped accesses (bit j: access j reads a row only committed
-    // prefix readers hold, k_kill's skip rule)
-    __shared__ uint32_t l_end[KEYS ? kKillTile : 1], l_fpre[KEYS ? kKillTile + 1 : 1];
-    __shared__ uint32_t l_skip[KEYS ? kKillTile : 1];
+    // KEYS: per tile txn its end; per survivor its whole length and, up to 32
+    // accesses, its skipped ones (bit j: access j reads a row only committed
+    // prefix readers hold, k_kill's skip rule); KEYS 1: the prefix of the
+    // survivors' whole lengths (the acc_row loop)
+    __shared__ uint32_t l_end[KEYS ? kKillTile : 1], l_fl[KEYS ? kKillTile : 1], l_skip[KEYS ? kKillTile : 1];
+    __shared__ uint32_t l_fpre[KEYS == 1 ? kKillTile + 1 : 1];
     const uint32_t m = n_txn > K ? n_txn - K : 0u;
     const uint32_t ntiles = (m + kKillTile - 1) / kKillTile;
     if (blockIdx.x >= ntiles || input_err(ctr) || ctr->halt) return;  // (b_txn = b_acc = 0 from the epoch clear)
@@ -479,7 +495,7 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
     }
     const Agg inc_c = wave_incl<OpPlain>(Agg{0u, 0u, cnt}, lane);
     const Agg inc_a = wave_incl<OpPlain>(Agg{0u, 0u, acc}, lane);
-    const Agg inc_f = KEYS ? wave_incl<OpPlain>(Agg{0u, 0u, full}, lane) : Agg{0u, 0u, 0u};
+    const Agg inc_f = KEYS == 1 ? wave_incl<OpPlain>(Agg{0u, 0u, full}, lane) : Agg{0u, 0u, 0u};
     if (lane == 63) {
         wt_c[wave] = inc_c;
         wt_a[wave] = inc_a;
@@ -506,7 +522,7 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
     }
     ls += wave_excl_from_incl<OpPlain>(inc_c, lane).c;
     la += wave_excl_from_incl<OpPlain>(inc_a, lane).c;
-    if constexpr (KEYS) lf += wave_excl_from_incl<OpPlain>(inc_f, lane).c;
+    if constexpr (KEYS == 1) lf += wave_excl_from_incl<OpPlain>(inc_f, lane).c;
     __syncthreads();
     const uint32_t sub0 = s_sub0;
 #pragma unroll
@@ -518,20 +534,26 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
         status_b[sub] = ST_UNDEC;
         l_a0[ls] = a0s[j];
         l_pre[ls] = la;
-        if constexpr (KEYS) {
+        if constexpr (KEYS) l_fl[ls] = fls[j];
+        if constexpr (KEYS == 1) {
             l_fpre[ls] = lf;
-            l_skip[ls] = 0;
+            l_skip[ls] = 0;  // (the acc_row loop sets the bits)
         }
+        // KEYS 2: the survivor's skip bits as one word, from at most two words
+        // of k_kill's (a longer survivor's kept accesses come from skip_bits
+        // themselves: nth_kept)
+        if constexpr (KEYS == 2)
+            l_skip[ls] = skip_bits && fls[j] <= 32u ? range_field(skip_bits, a0s[j], a0s[j] + fls[j]) : 0u;
         la += lens[j];
         lf += fls[j];
         ls++;
     }
     if (tid == 0) {
         l_pre[s_nsurv] = s_nacc;
-        if constexpr (KEYS) l_fpre[s_nsurv] = s_nfull;
+        if constexpr (KEYS == 1) l_fpre[s_nsurv] = s_nfull;
     }
     __syncthreads();
-    if constexpr (KEYS) {
+    if constexpr (KEYS == 1) {
         // every access of every survivor, one per thread: its acc_row word for
         // the execution (the skipped reads' included), the key probed here
         constexpr uint32_t kU = 4;
@@ -557,7 +579,7 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
             for (uint32_t u = 0; u < kU; u++) {
                 uint64_t row = 0;
                 if (g0 + u * kBlock + tid < nf)
-                    kk_row<KEYS == 2>(kk, key[u], row, ctr);  // (the kill found every key)
+                    kk_row<false>(kk, key[u], row, ctr);  // (the kill found every key)
                 rows[u] = (uint32_t)row;
             }
 #pragma unroll
@@ -609,7 +631,7 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
             uint32_t a = 0;
             if (g < na) {
                 if constexpr (KEYS) {  // the qv-th access of the survivor whose skip bit is clear
-                    if (l_fpre[lo + 1] - l_fpre[lo] <= 32u) {
+                    if (l_fl[lo] <= 32u) {
                         uint32_t kept = ~l_skip[lo];
                         for (uint32_t r = qv[u]; r; r--) kept &= kept - 1;
                         a = l_a0[lo] + (uint32_t)__builtin_ctz(kept);
@@ -620,7 +642,7 @@ __global__ __launch_bounds__(kBlock) void k_kill_emit(
                     a = skip_bits ? nth_kept(skip_bits, l_a0[lo], qv[u]) : l_a0[lo] + qv[u];
                 }
             }
-            if constexpr (KEYS) {  // (the row from the key: this block's acc_row stores may not be visible yet)
+            if constexpr (KEYS) {  // (the row from the key: KEYS 1, this block's acc_row stores may not be visible yet)
                 uint64_t row = 0;
                 uint32_t w = 0;
                 if (g < na) kk_row<KEYS == 2>(kk, kk_key(kk, a, w), row, ctr);
@@ -665,12 +687,12 @@ uint32_t grid_of(uint64_t n, uint32_t cap) {
 }  // namespace
 
 void launch_prefix_mark(hipStream_t s, uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                        const uint32_t *acc_row, uint32_t K, uint32_t *row_state, uint64_t rs_words, int nowait,
-                        Counters *ctr, const uint32_t *words) {
+                        const uint32_t *acc_row, const RecRows &rr, uint32_t K, uint32_t *row_state,
+                        uint64_t rs_words, int nowait, Counters *ctr, const uint32_t *words) {
     // (the bitmap and the Bloom filter after it were zeroed by k_epoch_clear)
     const uint32_t g = std::max<uint32_t>(1, std::min<uint32_t>((K + kMarkBlock - 1) / kMarkBlock, 64));
-    DV_LAUNCH(k_prefix_mark, g, kMarkBlock, 0, s, status, tb_start, tb_end, acc_row, K, row_state, rs_words - kBloomWords,
-                                           row_state + (rs_words - kBloomWords), nowait, ctr, words);
+    DV_LAUNCH(k_prefix_mark, g, kMarkBlock, 0, s, status, tb_start, tb_end, acc_row, rr, K, row_state,
+              rs_words - kBloomWords, row_state + (rs_words - kBloomWords), nowait, ctr, words);
 }
 
 uint32_t kill_tiles(uint32_t n_after) { return (n_after + kKillTile - 1) / kKillTile; }
@@ -688,7 +710,7 @@ void launch_kill_compact(hipStream_t s, const uint32_t *tb_start, const uint32_t
     if (!nt) return;
     const uint64_t nw = (n_acc + 63) / 64;
     const KillKeys k0 = kk ? *kk : KillKeys{};
-    uint32_t *ar = const_cast<uint32_t *>(acc_row);  // (k_kill_emit writes the survivors' with keys)
+    uint32_t *ar = const_cast<uint32_t *>(acc_row);  // (k_kill_emit<1> writes the survivors')
     // (144 KiB of LDS per block: one per CU, each loads the hot words and the filter once)
     const uint32_t kg = grid_of(nw * 64 / kKillWords / 4 + 1, 256);
     if (kk && k0.dense_lim)

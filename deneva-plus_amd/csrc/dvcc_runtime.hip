@@ -520,6 +520,11 @@ uint64_t row_space(const dv_ctx *c) {
     return c->rep_P ? (uint64_t)c->rep_P * c->tab[0].nbuckets : c->total_rows;
 }
 
+// the row words of this epoch's committed txns: read from its own records (a
+// prefix-kill epoch with its txn boundaries on a dense map, which writes no
+// acc_row) or, every other epoch, from acc_row
+RecRows epoch_rec_rows(const dv_ctx *c) { return rec_rows(c->tb_mode ? &c->pf_kk : nullptr); }
+
 int err_from_bits(uint32_t b) { return err_code_of(b); }
 
 // idle time after which an asynchronous workgroup yields: the
@@ -1710,7 +1715,8 @@ void enqueue_exec(dv_ctx *c, uint8_t *d_commit, bool prologue_done = false) {
         if (c->cfg.cc_alg == DV_CALVIN) {
             launch_route_rowq(c->stream, *c->route, c->pairs[c->sorted], c->el, c->ew, c->n_acc, c->status, c->ctr);
         } else {  // (the commit bytes too)
-            launch_route_txn(c->stream, *c->route, c->rs, c->re, c->acc_row, c->n_txn, c->status, c->ctr, d_commit);
+            launch_route_txn(c->stream, *c->route, c->rs, c->re, c->acc_row, epoch_rec_rows(c), c->n_txn, c->status,
+                             c->ctr, d_commit);
             return;
         }
     } else {
@@ -1726,8 +1732,8 @@ void enqueue_exec(dv_ctx *c, uint8_t *d_commit, bool prologue_done = false) {
             // (its dense test; only with table 0 the context's one table -- a
             // row of another table takes its key from the pkey column)
             const KillKeys dk = kill_keys(make_tables(c), nullptr, nullptr, nullptr);
-            launch_exec_txn(c->stream, c->rs, c->re, c->acc_row, c->n_txn, c->status, c->f0, c->pkey,
-                            c->cfg.cc_alg != DV_OCC, c->ctr, rm, d_commit,
+            launch_exec_txn(c->stream, c->rs, c->re, c->acc_row, epoch_rec_rows(c), c->n_txn, c->status, c->f0,
+                            c->pkey, c->cfg.cc_alg != DV_OCC, c->ctr, rm, d_commit,
                             dk.tabs.n == 1 && dk.dense_lim != 0 && dk.tabs.t[0].rep_part == kNoRep, dk.dense_base);
             return;
         }
@@ -2138,8 +2144,8 @@ int enqueue_survivors(dv_ctx *c) {
     const bool nowait = c->cfg.cc_alg != DV_OCC;
     const uint64_t rs_words = row_state_words(row_space(c));
     const uint32_t K = c->pf_K;
-    launch_prefix_mark(c->stream, c->status, c->rs, c->re, c->acc_row, K, c->row_state, rs_words, nowait,
-                       c->ctr, c->prefix_words ? c->tword : nullptr);
+    launch_prefix_mark(c->stream, c->status, c->rs, c->re, c->acc_row, epoch_rec_rows(c), K, c->row_state, rs_words,
+                       nowait, c->ctr, c->prefix_words ? c->tword : nullptr);
     launch_kill_compact(c->stream, c->rs, c->re, c->acc_row, c->pf_n_acc, c->pf_n_acc_dev, K, c->n_txn,
                         c->row_state, rs_words, nowait, c->kill_bits,
                         nowait ? c->kill_bits + kill_words(c->cfg.max_acc) : nullptr, c->status, c->b_map, c->b_status,
@@ -2232,6 +2238,11 @@ int run_prefix_epoch(dv_ctx *c, const dv_epoch_dev *ep) {
         c->rs = ep->txn_begin;
         c->re = ep->txn_begin + 1;
         c->pf_kk = kill_keys(make_tables(c), ep->keys, ep->types, ep->recs32);
+        // k_kill and row_word keep dense_base + key in 31 bits.  (dense_base is
+        // table 0's row_base: nonzero when another table was created first;
+        // create_table bounds the context's rows by kMaxRows, and a replicated
+        // epoch's row is its key, dense_base 0.)
+        if (c->pf_kk.dense_lim && c->pf_kk.dense_base + c->pf_kk.dense_lim > kMaxRows + 1) return DV_ERR_ARG;
     }
     rec(c, 0);
     const bool mir = c->mir_pending;  // (the previous pipelined epoch's read-back rides on this clear)
@@ -2246,7 +2257,7 @@ int run_prefix_epoch(dv_ctx *c, const dv_epoch_dev *ep) {
     if (c->tb_mode)
         launch_probe_tb(c->stream, make_tables(c), ep->keys, ep->types, ep->recs32, ep->txn_begin, ep->n_acc,
                         ep->n_txn, K,
-                        c->slog, c->pairs[0], c->tlen, c->acc_row, c->ctr,
+                        c->slog, c->pairs[0], c->tlen, epoch_rec_rows(c).on ? nullptr : c->acc_row, c->ctr,
                         c->cfg.cc_alg == DV_WAIT_DIE ? ep->ts : nullptr, ktiming(c) ? c->ev[kEvProbe0] : nullptr,
                         ktiming(c) ? c->ev[kEvProbe1] : nullptr, ep->n_acc_dev);
     else
