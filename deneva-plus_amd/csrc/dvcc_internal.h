@@ -614,6 +614,40 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    const uint32_t *precs = nullptr, uint32_t *orecs = nullptr, uint32_t *otb = nullptr,
                    const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr);
 
+// ---- Deneva client batches decoded on the device (dvcc_wire.hip)
+// k_wire_check takes kWireWave batches per workgroup (a wave each), the scan
+// kWireChunk batches per chunk, the reply compaction kReplyTile txns per tile.
+constexpr uint32_t kWireWave = 4;
+constexpr uint32_t kWireChunk = 256 * 12;  // (block_chunk_scan256's register path)
+constexpr uint32_t kWireMaxMsg = 40;       // messages of a 4,096-byte batch (100 bytes each at least)
+constexpr uint32_t kReplyTile = 256;
+// the per-call words of nb batches (device): carved from one allocation
+struct WireWs {
+    uint32_t *bt, *ba;      // [nb] txns / accesses per batch, then their prefix inside the chunk
+    uint8_t *bm;            // [nb] the batch's longest txn
+    uint16_t *moff;         // [nb * kWireMaxMsg] message offsets inside the batch
+    uint32_t *ct, *ca, *cm; // [chunks] per chunk: txns, accesses (then their prefixes), longest txn
+    uint32_t *first_bad;    // one word: the first malformed batch
+    dv_wire_dev_result *res;
+};
+uint64_t wire_ws_bytes(uint32_t nb);
+WireWs wire_ws_carve(void *base, uint32_t nb);
+// batches [first, first + nb) of buf checked, scanned and planned (the result
+// record complete in ws.res, the closing boundary and *n_acc_dev written) ...
+void launch_wire_plan(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
+                      const uint64_t *off, uint32_t first, uint32_t nb, uint32_t n_batches,
+                      const dv_wire_dev_out &out, uint64_t next_txn, const WireWs &ws);
+// ... and the taken ones decoded into out
+void launch_wire_emit(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
+                      uint32_t first, uint32_t nb, const dv_wire_dev_out &out, uint64_t next_txn,
+                      const WireWs &ws);
+// the committed txns' reply fields compacted in txn order; bc: reply_tiles(n_txn) + 1
+// words, bc[reply_tiles(n_txn)] = their count
+uint32_t reply_tiles(uint32_t n_txn);
+void launch_reply_fields(hipStream_t s, const uint8_t *commit, uint32_t n_txn, const uint64_t *txn_id,
+                         const uint64_t *cst, const uint32_t *rnode, uint64_t *o_txn_id, uint64_t *o_cst,
+                         uint32_t *o_rnode, uint32_t *bc);
+
 // ---- prefix-kill epochs (dvcc_prefix.hip)
 // the row-state bitmap (2 bits per row): its 32-bit words for `rows` rows;
 // launch_prefix_mark clears it and marks the committed prefix txns' rows

@@ -153,6 +153,15 @@ struct dv_ctx {
     uint32_t *carry_tot = nullptr;                   // its totals (kRefillTot words)
     uint32_t *gc_tb = nullptr;                       // dv_epoch_group_carry: a batch's ranges (2 x max_txn)
     uint32_t *gc_tot = nullptr;                      // ... 3 totals per batch (kMaxGroupBatches)
+    // dv_wire_ingest_device / dv_wire_reply_fields_device (dvcc_wire.hip): the
+    // per-call words of wire_nb batches, the reply compaction's tile counts,
+    // and the pinned words the two entries read back (the result record, the count)
+    uint8_t *wire_ws = nullptr;
+    uint32_t wire_nb = 0;
+    uint32_t *reply_bc = nullptr;
+    uint32_t reply_nt = 0;
+    dv_wire_dev_result *wire_h = nullptr;
+    hipEvent_t wire_ev = nullptr;
     DvComm *comm = nullptr;                          // RCCL communicator (dv_comm_init)
     uint32_t round_tag = 0;                          // descriptor tag of the last pass
     uint32_t ticket = 0;                             // next tile_ctr slot
@@ -701,6 +710,7 @@ void dv_close(dv_ctx *c) {
                     c->d_tables, c->d_commit, c->d_txn, c->d_grant, c->d_tb, c->split_err,
                     c->d_args, c->d_oid, c->tp_dsnap,
                     c->row_state, c->b_status, c->b_tlen, c->b_map, c->kinfo, c->ktsum, c->kill_bits, c->gc_tb, c->gc_tot,
+                    c->wire_ws, c->reply_bc,
                     c->hslot[0].acc, c->hslot[0].tb, c->hslot[1].acc, c->hslot[1].tb};
     for (void *b : bufs) dfree(b);
     for (auto &h : c->hslot) {
@@ -713,6 +723,8 @@ void dv_close(dv_ctx *c) {
     }
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
+    if (c->wire_h) (void)hipHostFree(c->wire_h);
+    if (c->wire_ev) (void)hipEventDestroy(c->wire_ev);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->sev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->pev) if (e) (void)hipEventDestroy(e);
@@ -3710,6 +3722,95 @@ int dv_tpcc_epoch_run(dv_ctx *c, const dv_access *acc, uint64_t n_acc, const uin
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return DV_OK;
+}
+
+// ---- Deneva client batches decoded on the device (dvcc_wire.hip)
+int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                          const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
+                          const dv_wire_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !buf || !off || !out || !res) return DV_ERR_ARG;
+    // TPC-C (dv_tpcc_expand, the last-name lists) and CALVIN (batch-id sequencing) stay on the host decoder
+    if (cfg->workload != DV_YCSB || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt) return DV_ERR_ARG;
+    if (!out->txn_begin || !out->n_acc_dev || !out->max_txn || out->max_txn > kMaxTxn) return DV_ERR_ARG;
+    const bool old_form = out->keys && out->types && out->acc_txn;
+    if (!old_form && (out->keys || out->types || out->acc_txn)) return DV_ERR_ARG;  // all three or none
+    if (!old_form && !out->recs32) return DV_ERR_ARG;
+    // a record holds a key below 2^31: the key range check then guarantees every record fits
+    if (out->recs32 && cfg->synth_table_size > (1ull << 31)) return DV_ERR_ARG;
+    if (first_batch > n_batches) return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // A taken batch holds a txn at least, so at most max_txn of them are taken
+    // and a stopper lies among the first max_txn + 1: the call looks no
+    // further (and every sum of 40 txns / 170 accesses a batch stays in 32 bits).
+    const uint32_t nb = std::min(n_batches - first_batch, out->max_txn + 1);
+    if (nb > c->wire_nb || !c->wire_ws) {  // (no captured graph names these words)
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dfree(c->wire_ws);
+        c->wire_ws = nullptr;
+        c->wire_nb = 0;
+        int r = dalloc(&c->wire_ws, wire_ws_bytes(nb));
+        if (r) return r;
+        c->wire_nb = nb ? nb : 1;
+    }
+    if (!c->wire_h) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
+    }
+    const WireWs ws = wire_ws_carve(c->wire_ws, c->wire_nb);
+    launch_wire_plan(c->stream, *cfg, buf, buf_len, off, first_batch, nb, n_batches, *out, next_txn, ws);
+    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(dv_wire_dev_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
+    launch_wire_emit(c->stream, *cfg, buf, off, first_batch, nb, *out, next_txn, ws);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone: the emit runs on
+    *res = *c->wire_h;
+    return res->status;
+}
+
+int dv_wire_reply_fields_device(dv_ctx *c, const uint8_t *commit, uint32_t n_txn, const uint64_t *txn_id,
+                                const uint64_t *client_startts, const uint32_t *return_node,
+                                uint64_t *out_txn_id, uint64_t *out_client_startts, uint32_t *out_return_node,
+                                uint32_t *n_out) {
+    KProfScope kps_(c);
+    if (!c || !n_out) return DV_ERR_ARG;
+    if (n_txn && (!commit || !txn_id || !client_startts || !return_node || !out_txn_id || !out_client_startts ||
+                  !out_return_node))
+        return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nt = reply_tiles(n_txn);
+    if (nt > c->reply_nt || !c->reply_bc) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dfree(c->reply_bc);
+        c->reply_bc = nullptr;
+        c->reply_nt = 0;
+        int r = dalloc(&c->reply_bc, (uint64_t)nt + 1);
+        if (r) return r;
+        c->reply_nt = nt;
+    }
+    if (!c->wire_h) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
+    }
+    launch_reply_fields(c->stream, commit, n_txn, txn_id, client_startts, return_node, out_txn_id,
+                        out_client_startts, out_return_node, c->reply_bc);
+    HIPCHK(hipGetLastError());
+    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(c->wire_h + 1);
+    HIPCHK(hipMemcpyAsync(h_cnt, c->reply_bc + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_out = *h_cnt;
+    return DV_OK;
+}
+
+int dv_epoch_reads_tb_only(const dv_ctx *c, uint32_t n_txn) {
+    if (!c) return DV_ERR_ARG;
+    static const uint32_t word = 0;  // (tb_epoch looks at which arrays are given, never through them)
+    dv_epoch_dev d{};
+    d.n_txn = n_txn;
+    d.txn_begin = d.recs32 = d.n_acc_dev = &word;
+    return tb_epoch(c, &d) ? 1 : 0;
 }
 
 }  // extern "C"

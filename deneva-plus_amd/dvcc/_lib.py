@@ -148,6 +148,19 @@ class WireCursor(ctypes.Structure):
                 ("left", ctypes.c_uint32), ("src", ctypes.c_uint32)]
 
 
+class WireDevOut(ctypes.Structure):  # dv_wire_dev_out: device output buffers of dv_wire_ingest_device
+    _fields_ = [("max_txn", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("max_acc", ctypes.c_uint64),
+                ("txn_begin", ctypes.c_void_p), ("n_acc_dev", ctypes.c_void_p), ("recs32", ctypes.c_void_p),
+                ("keys", ctypes.c_void_p), ("types", ctypes.c_void_p), ("acc_txn", ctypes.c_void_p),
+                ("owner", ctypes.c_void_p), ("txn_id", ctypes.c_void_p), ("client_startts", ctypes.c_void_p),
+                ("return_node", ctypes.c_void_p)]
+
+
+class WireDevResult(ctypes.Structure):  # dv_wire_dev_result
+    _fields_ = [("status", ctypes.c_int32), ("n_taken", ctypes.c_uint32), ("n_txn", ctypes.c_uint32),
+                ("max_txn_acc", ctypes.c_uint32), ("n_acc", ctypes.c_uint64), ("next_txn", ctypes.c_uint64)]
+
+
 # TPC-C table ids and operation words (include/dvcc.h)
 T_WAREHOUSE, T_DISTRICT, T_CUSTOMER, T_ITEM, T_STOCK, T_CUST_LAST = 0, 1, 2, 3, 4, 5
 TOP_NONE, TOP_PAY_WH, TOP_PAY_DIST, TOP_PAY_CUST, TOP_NO_DIST, TOP_NO_STOCK = 0, 1, 2, 3, 4, 5
@@ -247,6 +260,11 @@ SIGNATURES = [
                                               _P(ctypes.c_uint32), _P(WireEpoch)]),
     ("dv_wire_respond", ctypes.c_int, [_P(WireCfg), _P(WireEpoch), _vp, _vp, ctypes.c_uint64, _vp,
                                        ctypes.c_uint32, _P(ctypes.c_uint32)]),
+    ("dv_wire_ingest_device", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                             ctypes.c_uint32, _P(WireDevOut), ctypes.c_uint64, _P(WireDevResult)]),
+    ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _P(ctypes.c_uint32)]),
+    ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
 ]
 
 _lib = None

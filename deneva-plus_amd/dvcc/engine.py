@@ -133,6 +133,32 @@ class DeviceEpoch:
         return self
 
     @classmethod
+    def from_device_buffers(cls, recs32, txn_begin, n_acc_dev, n_txn, n_acc, max_txn_acc=0, keys=None, types=None,
+                            acc_txn=None):
+        """An epoch over caller-owned device tensors in tb form: 4-byte records
+        [>= n_acc], boundaries [>= n_txn + 1] and the access count's device
+        word (dv_epoch_dev::n_acc_dev; n_acc bounds it).  keys / types /
+        acc_txn: the same accesses in the other form, all three or none -- none
+        when the epoch takes the engine's tb-mode prefix path, which reads
+        records and boundaries alone (CCEngine.reads_tb_only); the descriptor
+        then names tensors allocated to the records' capacity, never read, as
+        ClosedLoopBufs does."""
+        import torch
+        self = cls.__new__(cls)
+        if keys is None:
+            cap, dev = max(1, int(recs32.numel())), recs32.device
+            keys = torch.empty(cap, dtype=torch.int64, device=dev)
+            types = torch.empty(cap, dtype=torch.uint8, device=dev)
+            acc_txn = torch.empty(cap, dtype=torch.int32, device=dev)
+        self.keys, self.types, self.acc_txn, self.tables = keys, types, acc_txn, None
+        self.txn_begin, self.recs32, self.n_acc_dev = txn_begin, recs32, n_acc_dev
+        self.n_acc = int(n_acc)
+        self.n_txn = int(n_txn)
+        self.max_txn_acc = int(max_txn_acc)
+        self.dense = None
+        return self
+
+    @classmethod
     def concat(cls, first, second):
         """`first`'s txns, then `second`'s (renumbered after them): the next
         epoch of the abort carry-over, carried txns ahead of the new ones."""
@@ -365,6 +391,15 @@ class CCEngine:
         the prefix size in txns."""
         v = 0xFFFFFFFF if prefix_txns is None else int(prefix_txns)
         L.check(L.lib().dv_set_prefix(self._ctx, v), "dv_set_prefix")
+
+    def reads_tb_only(self, n_txn):
+        """True when an epoch of n_txn txns given as records and boundaries
+        (DeviceEpoch.from_device_buffers) takes the tb-mode prefix-kill path,
+        which reads nothing else (dv_epoch_reads_tb_only)."""
+        rc = L.lib().dv_epoch_reads_tb_only(self._ctx, int(n_txn))
+        if rc < 0:
+            L.check(rc, "dv_epoch_reads_tb_only")
+        return rc == 1
 
     def set_timing(self, timing, profile=False):
         """Between epochs: True = per-stage events, "kernel" = only the scatter

@@ -6,7 +6,9 @@ YCSBClientQueryMessage / TPCCClientQueryMessage (transport/message.cpp:
 451-687, 856-916), or under CALVIN the sequencer's forwarded CL_QRY batches
 ended by RDONE -- decoded by libdvcc straight into the host arrays of an
 epoch, and the replies (CL_RSP to the clients, CALVIN_ACK to the sequencers)
-packed the same way from the epoch's commit bytes.
+packed the same way from the epoch's commit bytes.  DeviceWireIngress does
+the YCSB ingress on the device instead (dv_wire_ingest_device): the receive
+queue's bytes in, a device-resident epoch out.
 """
 import ctypes
 from dataclasses import dataclass
@@ -14,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .engine import Epoch, _ptr
+from .engine import DeviceEpoch, Epoch, _ptr
 
 
 @dataclass
@@ -149,6 +151,127 @@ class WireIngress:
         L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
                                         _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
         return [out[int(off[b]):int(off[b + 1])].tobytes() for b in range(nb.value)]
+
+
+class DeviceWireIngress:
+    """dv_wire_ingest_device / dv_wire_reply_fields_device over device
+    buffers of max_txn txns and max_acc accesses on `engine`'s context (YCSB,
+    NO_WAIT / WAIT_DIE / OCC).  feed_buffer decodes a receive queue's batches
+    into a DeviceEpoch, whole batches at a time; respond packs the replies of
+    its committed txns.  The epoch's tensors are the ingress's own: the next
+    feed_buffer overwrites them."""
+
+    def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
+                 device="cuda"):
+        import torch
+        self.engine = engine
+        self.cfg = L.WireCfg(L.YCSB, 0, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
+        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
+        self.next_txn = 0
+        A, T = max(1, self.max_acc), self.max_txn
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
+        self.txn_begin, self.n_acc_dev = new(T + 1, torch.int32), new(1, torch.int32)
+        # 4-byte records hold keys below 2^31 (dv_epoch_dev::recs32)
+        self.recs32 = new(A, torch.int32) if synth_table_size <= 1 << 31 else None
+        self.keys = self.types = self.acc_txn = None  # (allocated by the first epoch that needs them)
+        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
+        self.return_node = new(T, torch.int32)
+        self._dev = device
+
+    def _old_form(self):
+        import torch
+        if self.keys is None:
+            A = max(1, self.max_acc)
+            self.keys = torch.empty(A, dtype=torch.int64, device=self._dev)
+            self.types = torch.empty(A, dtype=torch.uint8, device=self._dev)
+            self.acc_txn = torch.empty(A, dtype=torch.int32, device=self._dev)
+
+    def _ingest(self, buf, off, first_batch, old):
+        out = L.WireDevOut(self.max_txn, 0, self.max_acc, self.txn_begin.data_ptr(), self.n_acc_dev.data_ptr(),
+                           self.recs32.data_ptr() if self.recs32 is not None else None,
+                           self.keys.data_ptr() if old else None, self.types.data_ptr() if old else None,
+                           self.acc_txn.data_ptr() if old else None, None, self.txn_id.data_ptr(),
+                           self.client_startts.data_ptr(), self.return_node.data_ptr())
+        res = L.WireDevResult()
+        rc = L.lib().dv_wire_ingest_device(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(), buf.numel(),
+                                           off.data_ptr(), off.numel() - 1, first_batch, ctypes.byref(out),
+                                           self.next_txn, ctypes.byref(res))
+        if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or (rc == L.DV_ERR_ARG and res.status != rc):
+            L.check(rc, "dv_wire_ingest_device")  # (refused before any launch, or a HIP failure)
+        return res
+
+    def feed_buffer(self, buf, off, first_batch=0):
+        """Batches first_batch.. of buf (a torch uint8 device tensor, or a numpy
+        array, uploaded) at offsets off (u64 [n + 1], numpy or an int64 device
+        tensor) -> (epoch, n_taken, status).  status DV_OK: all taken;
+        WIRE_MORE: the epoch is full, call again with first_batch = n_taken;
+        DV_ERR_ARG: batch n_taken is malformed (or alone exceeds the
+        capacity); the epoch holds the batches before it.  The epoch is
+        written on the engine's stream (run it there; other streams
+        synchronise first) and carries the device reply arrays."""
+        import torch
+        if isinstance(buf, np.ndarray):
+            buf = torch.from_numpy(np.ascontiguousarray(buf, np.uint8)).to(self._dev)
+        if isinstance(off, np.ndarray):
+            off = torch.from_numpy(np.ascontiguousarray(off, np.uint64).view(np.int64)).to(self._dev)
+        self.engine._after_torch()
+        # records and boundaries alone when the epoch takes the tb-mode prefix
+        # path, both forms otherwise -- as loop_form picks for the closed loop.
+        # The path depends on the epoch's size, known once it is decoded: a
+        # short last epoch is decoded again with both forms.
+        old = self.recs32 is None or not self.engine.reads_tb_only(self.max_txn)
+        if old:
+            self._old_form()
+        res = self._ingest(buf, off, first_batch, old)
+        if not old and not self.engine.reads_tb_only(res.n_txn):
+            old = True
+            self._old_form()
+            res = self._ingest(buf, off, first_batch, old)
+        self._held = (buf, off)  # (the decode may still read them when this returns)
+        self.next_txn = res.next_txn
+        n, a = res.n_txn, res.n_acc
+        if self.recs32 is not None:
+            ep = DeviceEpoch.from_device_buffers(self.recs32, self.txn_begin, self.n_acc_dev, n, a, res.max_txn_acc,
+                                                 self.keys if old else None, self.types if old else None,
+                                                 self.acc_txn if old else None)
+        else:
+            ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n,
+                                          max_txn_acc=res.max_txn_acc)
+        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
+        return ep, res.n_taken, res.status
+
+    def respond(self, ep, d_commit):
+        """The CL_RSP batches (bytes) of the epoch's committed txns (d_commit:
+        device commit bytes): their reply fields compacted on the device, then
+        the host packer (dv_wire_respond) over them."""
+        import torch
+        n = ep.n_txn
+        tid = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
+        cst = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
+        rn = torch.empty(max(1, n), dtype=torch.int32, device=self._dev)
+        cnt = ctypes.c_uint32()
+        self.engine._after_torch()
+        L.check(L.lib().dv_wire_reply_fields_device(self.engine._ctx, d_commit.data_ptr(), n, ep.txn_id.data_ptr(),
+                                                    ep.client_startts.data_ptr(), ep.return_node.data_ptr(),
+                                                    tid.data_ptr(), cst.data_ptr(), rn.data_ptr(),
+                                                    ctypes.byref(cnt)), "dv_wire_reply_fields_device")
+        c = cnt.value
+        if not c:
+            return []
+        e = L.WireEpoch()
+        e.n_txn, e.max_txn, e.batch_id = c, c, (1 << 64) - 1
+        h_tid, h_cst, h_rn = tid[:c].cpu().numpy(), cst[:c].cpu().numpy(), rn[:c].cpu().numpy()
+        e.txn_id, e.client_startts, e.return_node = h_tid.ctypes.data, h_cst.ctypes.data, h_rn.ctypes.data
+        cm = np.ones(max(1, c), np.uint8)
+        # (a batch holds (MSG_MAX - 12) // message size replies; one partial batch per destination)
+        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 7 * 8 + 8)
+        max_b = c // per + len(np.unique(h_rn)) + 1
+        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
+        off = np.zeros(max_b + 1, np.uint64)
+        nb = ctypes.c_uint32()
+        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
+                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
+        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

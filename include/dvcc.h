@@ -59,6 +59,9 @@
  *   dv_wire_respond             CL_RSP / CALVIN_ACK replies (worker_thread.cpp:127-152;
  *                               message.cpp:921-949, 1057-1110) packed as MessageThread does
  *                               (transport/msg_thread.cpp:53-111)
+ *   dv_wire_ingest_device /     the same receive path for YCSB client batches already in
+ *   dv_wire_reply_fields_device device memory, into a device epoch; the committed txns'
+ *                               reply fields compacted for dv_wire_respond
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
  * the final table state equal a single worker thread running the same epoch
@@ -937,6 +940,77 @@ int dv_wire_decode_batches(const dv_wire_cfg *cfg, const uint8_t *buf, const uin
  * txn_id / return_node (and, not CALVIN, client_startts) arrays. */
 int dv_wire_respond(const dv_wire_cfg *cfg, const dv_wire_epoch *ep, const uint8_t *commit, uint8_t *out,
                     uint64_t cap, uint64_t *batch_off, uint32_t max_batches, uint32_t *n_batches);
+
+/* ---- the same ingress on the device (dvcc_wire.hip): a receive queue's bytes
+ * as they are, in device memory, into a device-resident epoch.  YCSB without
+ * CALVIN only (TPC-C needs dv_tpcc_expand and the last-name lists on the
+ * host, CALVIN its batch-id sequencing: DV_ERR_ARG, use the host decoder).
+ * The caller's device output buffers and their capacities: */
+typedef struct dv_wire_dev_out {
+    uint32_t max_txn, pad_;      /* 1 .. 2^24                                              */
+    uint64_t max_acc;
+    uint32_t *txn_begin;         /* [max_txn + 1]                                          */
+    uint32_t *n_acc_dev;         /* one word: the epoch's access count (dv_epoch_dev::n_acc_dev) */
+    uint32_t *recs32;            /* [max_acc] optional: key | write << 31 (dv_epoch_dev::recs32;
+                                    needs cfg->synth_table_size <= 2^31)                   */
+    uint64_t *keys;              /* [max_acc] optional, with types and acc_txn: all three or none; */
+    uint8_t *types;              /*   at least one of the two access forms is given       */
+    uint32_t *acc_txn;
+    uint8_t *owner;              /* [max_acc] optional: key % part_cnt                     */
+    uint64_t *txn_id;            /* [max_txn] optional                                     */
+    uint64_t *client_startts;    /* [max_txn] optional                                     */
+    uint32_t *return_node;       /* [max_txn] optional: the batch's src                    */
+} dv_wire_dev_out;
+
+typedef struct dv_wire_dev_result {
+    int32_t status;              /* what the call returns: DV_OK, DV_WIRE_MORE, DV_ERR_ARG */
+    uint32_t n_taken;            /* the first batch not taken (n_batches: all were)        */
+    uint32_t n_txn;
+    uint32_t max_txn_acc;        /* the longest taken txn (dv_epoch_dev::max_txn_acc)      */
+    uint64_t n_acc;
+    uint64_t next_txn;           /* the next call's: next_txn + n_txn                      */
+} dv_wire_dev_result;
+
+/* Batches first_batch, first_batch + 1, ... of buf (device bytes, any
+ * alignment; batch b is buf[off[b] .. off[b + 1]), off: device u64[n_batches + 1])
+ * are taken whole and in order, with dv_wire_decode_batches' outputs for the
+ * same batches bit for bit (txn k of the call gets id node_id + node_cnt *
+ * (next_txn + k)), until
+ *   - all are taken: DV_OK;
+ *   - the next batch's txns or accesses do not fit max_txn / max_acc:
+ *     DV_WIRE_MORE, res->n_taken names it -- run the epoch and call again with
+ *     first_batch = n_taken and next_txn = res->next_txn (DV_ERR_ARG when it is
+ *     first_batch itself: it would never fit);
+ *   - the next batch is malformed -- whatever dv_wire_open refuses, or an off
+ *     that decreases or points past buf_len: DV_ERR_ARG, res->n_taken names it,
+ *     the batches before it are decoded and no byte of it reaches an output.
+ * The stopper that comes first in batch order decides.  Nothing is written at
+ * or past txn n_txn (txn_begin: n_txn + 1) or access n_acc.  Queued on the
+ * context's stream; the call waits for the result record alone, and an epoch
+ * over these buffers runs on the same context with no other synchronisation
+ * (other streams order themselves after the context's).  Arguments refused
+ * before any launch (DV_ERR_ARG, *res untouched): a null pointer, TPC-C or
+ * CALVIN, neither access form, keys / types / acc_txn not all three, recs32
+ * with synth_table_size > 2^31, max_txn outside 1 .. 2^24, first_batch >
+ * n_batches, zero part_cnt / node_cnt. */
+int dv_wire_ingest_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                          const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
+                          const dv_wire_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res);
+/* The reply fields of the committed txns (commit[t] != 0, device bytes) of an
+ * epoch ingested on the device: txn_id / client_startts / return_node
+ * (device, [n_txn]) compacted in txn order into out_* (device or host-mapped,
+ * n_txn entries each), *n_out = their count.  dv_wire_respond over those
+ * arrays with all-ones commit bytes packs the replies.  Queued on the
+ * context's stream; returns when the arrays are written. */
+int dv_wire_reply_fields_device(dv_ctx *ctx, const uint8_t *commit, uint32_t n_txn, const uint64_t *txn_id,
+                                const uint64_t *client_startts, const uint32_t *return_node,
+                                uint64_t *out_txn_id, uint64_t *out_client_startts, uint32_t *out_return_node,
+                                uint32_t *n_out);
+/* 1 when an epoch of n_txn txns given as records and boundaries alone
+ * (recs32, txn_begin, n_acc_dev) would take this context's tb-mode
+ * prefix-kill path, which reads nothing else; 0 when it also needs keys /
+ * types / acc_txn (what dv_wire_dev_out must then carry). */
+int dv_epoch_reads_tb_only(const dv_ctx *ctx, uint32_t n_txn);
 
 #ifdef __cplusplus
 }
