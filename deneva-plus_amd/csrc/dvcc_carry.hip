@@ -308,6 +308,130 @@ __global__ __launch_bounds__(kBlock) void k_refill_fresh(const uint64_t *__restr
     }
 }
 
+// ---- the loop tracker (dv_closed_loop_track): identity through the refill.
+// One 8-byte word per txn, src | born << 32.  k_track_carry runs behind
+// k_refill_plan (bt[] and tot[] final).  A wave takes one 256-txn carry block,
+// a lane four consecutive txns (32 contiguous bytes of identity words), so a
+// txn's rank in its block is a wave scan -- no barrier on the way.  A carried
+// txn's word moves to its new number, bt[b] plus that rank as in k_carry_copy;
+// a committed txn's word goes to the commit log at the running count plus its
+// rank among the epoch's commits, t - (carried before t) -- positions at or
+// past log_cap are counted and not written.  Retries at commit, (k - born) /
+// L, go into a histogram in LDS, flushed once per block with one atomic per
+// non-empty bin, the block's counts with one atomic each -- not into the
+// caller's arrays but into one of kTrackSlots copies (tr.part): every block of
+// a 1M-txn epoch adding to the same 8-byte words took 126 us, 30 ns per block
+// and address, one after the other.  k_track_fresh, the next launch, folds the
+// copies into the histogram and the totals with plain stores and clears them.
+// Every block reads *log_pos, so nobody in this launch writes it: one thread
+// leaves the new count in the epoch's epoch_end slot and k_track_fresh copies
+// it to *log_pos.
+constexpr uint32_t kTrackPer = 4;  // txns per lane: a wave covers kCarryTpb
+static_assert(kTrackPer * 64 == kCarryTpb, "a wave of k_track_carry takes one carry block");
+
+__global__ __launch_bounds__(kBlock) void k_track_carry(const uint8_t *__restrict__ status, uint32_t n_txn,
+                                                        const uint32_t *__restrict__ bt,
+                                                        const uint32_t *__restrict__ tot, uint32_t n_out,
+                                                        RefillTrack tr) {
+    __shared__ uint32_t s_hist[kTrackBins];
+    __shared__ uint32_t s_tot[4];  // committed, aborted, first aborts, most retries
+    if (tot[4]) return;            // (a refill behind a halted epoch: k_refill_plan)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t i = tid; i < tr.n_bins; i += kBlock) s_hist[i] = 0;
+    if (tid < 4) s_tot[tid] = 0;
+    __syncthreads();
+    const uint32_t b = blockIdx.x * (kBlock / 64) + wave;  // the wave's carry block (past the last: idle)
+    const uint64_t t0 = (uint64_t)b * kCarryTpb + lane * kTrackPer;
+    const uint32_t nv = t0 >= n_txn ? 0u : (n_txn - t0 < kTrackPer ? (uint32_t)(n_txn - t0) : kTrackPer);
+    uint64_t word[kTrackPer];
+    bool cr[kTrackPer];
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kTrackPer; j++) {
+        word[j] = j < nv ? tr.ids[t0 + j] : 0;
+        cr[j] = j < nv && carried(status, (uint32_t)(t0 + j));
+        c += cr[j] ? 1u : 0u;
+    }
+    uint32_t incl = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += o;
+    }
+    // txns carried before this lane's first, in the whole epoch
+    uint32_t r = ((uint64_t)b * kCarryTpb < n_txn ? bt[b] : 0u) + incl - c;
+    const uint32_t pos0 = *tr.log_pos;
+    uint32_t n_cm = 0, n_first = 0, mx = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kTrackPer; j++) {
+        if (j >= nv) continue;
+        const uint32_t born = (uint32_t)(word[j] >> 32);
+        if (cr[j]) {
+            if (r < n_out) tr.oids[r] = word[j];
+            r++;
+            n_first += born == tr.k ? 1u : 0u;
+            continue;
+        }
+        const uint64_t pos = (uint64_t)pos0 + ((uint32_t)(t0 + j) - r);
+        if (pos < tr.log_cap) tr.log[pos] = word[j];
+        const uint32_t retries = (tr.k - born) / tr.L;
+        atomicAdd(&s_hist[retries < tr.n_bins - 1 ? retries : tr.n_bins - 1], 1u);
+        mx = retries > mx ? retries : mx;
+        n_cm++;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n_cm += __shfl_xor(n_cm, off, 64);
+        c += __shfl_xor(c, off, 64);
+        n_first += __shfl_xor(n_first, off, 64);
+        const uint32_t o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+    }
+    if (lane == 0) {
+        if (n_cm) atomicAdd(&s_tot[0], n_cm);
+        if (c) atomicAdd(&s_tot[1], c);
+        if (n_first) atomicAdd(&s_tot[2], n_first);
+        if (mx) atomicMax(&s_tot[3], mx);
+    }
+    __syncthreads();
+    uint32_t *const part = tr.part + (size_t)(blockIdx.x % kTrackSlots) * (tr.n_bins + 4);
+    for (uint32_t i = tid; i < tr.n_bins; i += kBlock)
+        if (s_hist[i]) atomicAdd(&part[i], s_hist[i]);
+    if (tid < 3 && s_tot[tid]) atomicAdd(&part[tr.n_bins + tid], s_tot[tid]);
+    if (tid == 3 && s_tot[3]) atomicMax(&part[tr.n_bins + 3], s_tot[3]);
+    if (blockIdx.x == 0 && tid == 0) *tr.epoch_end = pos0 + (n_txn - tot[2]);
+}
+
+// the F fresh txns' identity words behind the C carried ones: their pool index
+// and the number of the epoch being built; and (prev: there was an epoch to
+// log) what k_track_carry left -- the commit count, and the kTrackSlots copies
+// of the histogram and the counts, added to the caller's (one thread a word:
+// plain 8-byte stores) and cleared for the next refill
+__global__ __launch_bounds__(kBlock) void k_track_fresh(const uint32_t *__restrict__ tot, uint32_t n_out,
+                                                        uint32_t pool_n, int prev, RefillTrack tr) {
+    if (tot[4]) return;
+    const uint32_t C = tot[2] < n_out ? tot[2] : n_out, cur = tot[3], F = tot[5];
+    for (uint32_t f = blockIdx.x * kBlock + threadIdx.x; f < F && C + f < n_out; f += gridDim.x * kBlock)
+        tr.oids[C + f] = (((uint64_t)cur + f) % pool_n) | (uint64_t)tr.k_next << 32;
+    if (!prev) return;
+    const uint32_t stride = tr.n_bins + 4;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < stride; i += gridDim.x * kBlock) {
+        const bool is_max = i == tr.n_bins + 3;
+        uint32_t v[kTrackSlots], sum = 0;
+#pragma unroll
+        for (uint32_t sl = 0; sl < kTrackSlots; sl++) v[sl] = tr.part[sl * stride + i];  // (all in flight)
+#pragma unroll
+        for (uint32_t sl = 0; sl < kTrackSlots; sl++) {
+            sum = is_max ? (v[sl] > sum ? v[sl] : sum) : sum + v[sl];
+            if (v[sl]) tr.part[sl * stride + i] = 0;
+        }
+        if (!sum) continue;
+        uint64_t *const w = i < tr.n_bins ? &tr.hist[i] : &tr.totals[i - tr.n_bins];
+        *w = is_max ? (*w > sum ? *w : (uint64_t)sum) : *w + sum;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *tr.log_pos = *tr.epoch_end;
+}
+
 void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
                    uint32_t n_txn, const uint64_t *keys, const uint8_t *types, const uint8_t *tables,
                    const uint64_t *pkeys, const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptxn,
@@ -315,7 +439,7 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
                    uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs,
                    const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const uint64_t *args,
-                   const uint64_t *pargs, uint64_t *oargs) {
+                   const uint64_t *pargs, uint64_t *oargs, const RefillTrack *trk) {
     const uint32_t nb = carry_blocks(n_txn);
     if (nb) {
         DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba);
@@ -338,6 +462,12 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
     else
         DV_LAUNCH((k_refill_fresh<false>), grid, kBlock, 0, s, pkeys, ptypes, ptables, ptxn, ptb, pool_n, tot, n_out,
                   okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb, no_args, oargs);
+    if (!trk) return;
+    constexpr uint32_t wpb = kBlock / 64;  // (k_track_carry: a wave per carry block)
+    if (nb) DV_LAUNCH(k_track_carry, (nb + wpb - 1) / wpb, kBlock, 0, s, status, n_txn, bt, tot, n_out, *trk);
+    const uint32_t gf = (n_out + kBlock - 1) / kBlock;
+    DV_LAUNCH(k_track_fresh, gf < 1 ? 1 : (gf > 1024 ? 1024 : gf), kBlock, 0, s, tot, n_out, pool_n, nb ? 1 : 0,
+              *trk);
 }
 
 // a client batch's per-txn access ranges from its acc_txn (non-decreasing;

@@ -605,6 +605,27 @@ void launch_txn_ranges(hipStream_t s, const uint32_t *acc_txn, uint64_t n, uint3
 // tb form): the operation words of the carried (args) and fresh (pargs)
 // accesses too.
 constexpr uint32_t kRefillTot = 6;
+// The loop tracker's words for one refill (dv_closed_loop_track): the previous
+// epoch's identity words (ids; NULL with no previous epoch) and the next
+// one's (oids), the commit log, and the epoch numbers -- k: the epoch just
+// decided, k_next: the one being built, L: epochs until an abort returns.
+// Two more launches behind the refill's, no-ops under the same skip word.
+// part: the context's kTrackSlots copies of (n_bins + 4) words, all zero
+// between refills (k_track_carry adds to one copy per block, k_track_fresh
+// folds them into hist / totals and clears them).
+constexpr uint32_t kTrackBins = 1024;  // (the histogram's bins in LDS)
+constexpr uint32_t kTrackSlots = 32;
+struct RefillTrack {
+    const uint64_t *ids;
+    uint64_t *oids, *log;
+    uint32_t log_cap;
+    uint32_t *log_pos, *epoch_end;  // epoch_end: epoch k's own slot
+    uint64_t *hist;
+    uint32_t n_bins;
+    uint64_t *totals;
+    uint32_t k, k_next, L;
+    uint32_t *part;
+};
 void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
                    uint32_t n_txn, const uint64_t *keys, const uint8_t *types, const uint8_t *tables,
                    const uint64_t *pkeys, const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptxn,
@@ -612,7 +633,8 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
                    uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs = nullptr,
                    const uint32_t *precs = nullptr, uint32_t *orecs = nullptr, uint32_t *otb = nullptr,
-                   const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr);
+                   const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr,
+                   const RefillTrack *trk = nullptr);
 
 // ---- Deneva client batches decoded on the device (dvcc_wire.hip)
 // k_wire_check takes kWireWave batches per workgroup (a wave each), the scan

@@ -151,6 +151,15 @@ struct dv_ctx {
     uint32_t *carry_b = nullptr;                     // abort carry-over: block counts (2 x carry_nb)
     uint32_t carry_nb = 0;
     uint32_t *carry_tot = nullptr;                   // its totals (kRefillTot words)
+    // dv_closed_loop_track: the attached tracker (its struct and ids pointers
+    // copied) and the loop epoch number of the next call's first epoch
+    struct LoopTrk {
+        bool on = false;
+        dv_loop_track t{};
+        std::vector<uint64_t *> ids;
+        uint32_t next = 0;
+    } trk;
+    uint32_t *trk_part = nullptr;  // RefillTrack::part (allocated by the first attachment, zero between refills)
     uint32_t *gc_tb = nullptr;                       // dv_epoch_group_carry: a batch's ranges (2 x max_txn)
     uint32_t *gc_tot = nullptr;                      // ... 3 totals per batch (kMaxGroupBatches)
     // dv_wire_ingest_device / dv_wire_reply_fields_device (dvcc_wire.hip): the
@@ -705,7 +714,7 @@ void dv_close(dv_ctx *c) {
     void *bufs[] = {c->f0, c->pkey, c->ktag, c->pairs[0], c->pairs[1], c->el, c->ew, c->counts,
                     c->digit_tot, c->rel[0], c->rel[1], c->vb8, c->tlen, c->acc_row,
                     c->ulist[0], c->ulist[1], c->tb_start, c->tb_end, c->desc, c->tile_ctr,
-                    c->abounds, c->tword, c->carry_b, c->carry_tot,
+                    c->abounds, c->tword, c->carry_b, c->carry_tot, c->trk_part,
                     c->status, c->verdict, c->ctr, c->d_acc, c->d_keys, c->d_types,
                     c->d_tables, c->d_commit, c->d_txn, c->d_grant, c->d_tb, c->split_err,
                     c->d_args, c->d_oid, c->tp_dsnap,
@@ -3090,7 +3099,7 @@ LoopForm loop_form(const dv_ctx *c, const dv_epoch_dev *pool, const dv_epoch_dev
 // all fresh), then fresh ones from the pool, in the forms f names
 void enqueue_refill(dv_ctx *c, const dv_epoch_dev *prev, const dv_epoch_dev *prev_buf, const dv_epoch_dev *pool,
                     const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_out, const dv_epoch_dev &out,
-                    LoopForm f = {}) {
+                    LoopForm f = {}, const RefillTrack *trk = nullptr) {
     launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u,
                   prev && f.old ? prev->keys : nullptr, prev && f.old ? prev->types : nullptr,
                   prev && f.old ? prev->tables : nullptr, pool->keys, pool->types, pool->tables, pool->acc_txn,
@@ -3100,7 +3109,38 @@ void enqueue_refill(dv_ctx *c, const dv_epoch_dev *prev, const dv_epoch_dev *pre
                   const_cast<uint32_t *>(out.n_acc_dev), c->carry_b, c->carry_b + c->carry_nb, c->carry_tot,
                   prev ? c->ctr : nullptr, f.tb && prev_buf ? prev_buf->recs32 : nullptr,
                   f.tb ? pool->recs32 : nullptr, f.tb ? const_cast<uint32_t *>(out.recs32) : nullptr,
-                  f.tb ? const_cast<uint32_t *>(out.txn_begin) : nullptr);
+                  f.tb ? const_cast<uint32_t *>(out.txn_begin) : nullptr, nullptr, nullptr, nullptr, trk);
+}
+
+// The loop tracker (dv_closed_loop_track) of context t for one refill: behind
+// the call's epoch k (prev; none for a loop's first refill), building the
+// call's epoch k_next; ib / ob: their buffers' places in the loop's bufs; L:
+// epochs until an abort returns.  NULL when nothing is attached.
+const RefillTrack *track_at(const dv_ctx *t, bool prev, uint32_t k, uint32_t k_next, uint32_t ib, uint32_t ob,
+                            uint32_t L, RefillTrack *w) {
+    if (!t->trk.on) return nullptr;
+    const dv_loop_track &d = t->trk.t;
+    w->ids = prev ? t->trk.ids[ib] : nullptr;
+    w->oids = t->trk.ids[ob];
+    w->log = d.log;
+    w->log_cap = d.log_cap;
+    w->log_pos = d.log_pos;
+    w->epoch_end = d.epoch_end + (prev ? t->trk.next + k - d.first_epoch : 0u);
+    w->hist = d.retry_hist;
+    w->n_bins = d.n_bins;
+    w->totals = d.totals;
+    w->k = t->trk.next + k;
+    w->k_next = t->trk.next + k_next;
+    w->L = L;
+    w->part = t->trk_part;
+    return w;
+}
+// a loop call over n_bufs buffers and n_epochs epochs against the attachment
+int track_check(const dv_ctx *t, uint32_t n_bufs, uint32_t n_epochs) {
+    if (!t->trk.on) return DV_OK;
+    const dv_loop_track &d = t->trk.t;
+    if (d.n_bufs != n_bufs || n_epochs > d.epoch_cap - (t->trk.next - d.first_epoch)) return DV_ERR_ARG;
+    return DV_OK;
 }
 
 }  // namespace
@@ -3122,10 +3162,12 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].n_acc_dev ||
             (pool->tables && !bufs[b].tables))
             return DV_ERR_ARG;
+    if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     int r = carry_bufs(c, carry_blocks(n_txn));
     if (r) return r;
     const LoopForm form = loop_form(c, pool, bufs, 2, n_txn);
+    RefillTrack tw;
     // epoch k's descriptor: buffer k & 1, its access count on the device
     auto desc = [&](uint32_t k) {
         dv_epoch_dev d = bufs[k & 1];
@@ -3144,7 +3186,9 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         (void)hipStreamSynchronize(c->stream);
         return e;
     };
-    if (!resume) enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, bufs[0], form);
+    if (!resume)
+        enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, bufs[0], form,
+                       track_at(c, false, 0, 0, 0, 0, 1, &tw));
     const dv_epoch_dev d0 = desc(0);
     const bool pipelined = prefix_applies(c, &d0) && !timing(c) && !ktiming(c) && !c->rep_P;
     EpochSnap snap[2];
@@ -3154,7 +3198,8 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         const dv_epoch_dev d = desc(k);
         int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, stats_of(k));
         if (!e) {
-            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form);
+            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
+                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw));
             e = hip_fail(hipGetLastError(), "refill");
         }
         return e;
@@ -3171,7 +3216,8 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         if (!r) {
             // behind the execution: epoch k + 1 from epoch k's final statuses (a
             // no-op when k halted -- the host redoes both below)
-            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form);
+            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
+                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw));
             r = hip_fail(hipGetLastError(), "refill");
         }
         if (r) {
@@ -3212,6 +3258,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
+    c->trk.next += c->trk.on ? n_epochs : 0u;
     return DV_OK;
 }
 
@@ -3240,6 +3287,7 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
         if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].tables || !bufs[b].n_acc_dev ||
             !buf_args[b])
             return DV_ERR_ARG;
+    if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     int r = carry_bufs(c, carry_blocks(n_txn));
     if (r) return r;
@@ -3253,9 +3301,11 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
         d.ts = nullptr;  // (sequence order: carried txns first keep their priority)
         return d;
     };
-    // prev's aborted txns (NULL: none), then fresh pool txns, into buffer `into`
-    auto refill = [&](const dv_epoch_dev *prev, const uint64_t *prev_args, int into) {
+    // prev's aborted txns (NULL: none; k: its place in this call), then fresh
+    // pool txns, into buffer `into`
+    auto refill = [&](const dv_epoch_dev *prev, const uint64_t *prev_args, int into, uint32_t k) {
         const dv_epoch_dev &o = bufs[into];
+        RefillTrack tw;
         launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u, prev ? prev->keys : nullptr,
                       prev ? prev->types : nullptr, prev ? prev->tables : nullptr, pool->keys, pool->types,
                       pool->tables, pool->acc_txn, pool_begin, pool->n_txn, cursor, n_txn, bound,
@@ -3263,21 +3313,24 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
                       const_cast<uint32_t *>(o.acc_txn), const_cast<uint8_t *>(o.tables),
                       const_cast<uint32_t *>(o.n_acc_dev), c->carry_b, c->carry_b + c->carry_nb, c->carry_tot,
                       prev ? c->ctr : nullptr, nullptr, nullptr, nullptr, nullptr, prev_args, pool_args,
-                      buf_args[into]);
+                      buf_args[into],
+                      track_at(c, prev != nullptr, k, prev ? k + 1 : 0u, (uint32_t)(into ^ 1), (uint32_t)into, 1,
+                               &tw));
         return hip_fail(hipGetLastError(), "refill");
     };
-    if (!resume) r = refill(nullptr, nullptr, 0);
+    if (!resume) r = refill(nullptr, nullptr, 0, 0);
     for (uint32_t k = 0; !r && k < n_epochs; k++) {
         const dv_epoch_dev d = desc(k);
         r = dv_tpcc_epoch_run_device(c, &d, buf_args[k & 1], d_commits ? d_commits[k] : nullptr,
                                      d_oids ? d_oids[k] : nullptr, sts ? &sts[k] : nullptr);
-        if (!r) r = refill(&d, buf_args[k & 1], (int)((k + 1) & 1));
+        if (!r) r = refill(&d, buf_args[k & 1], (int)((k + 1) & 1), k);
     }
     if (r) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
+    c->trk.next += c->trk.on ? n_epochs : 0u;
     return DV_OK;
 }
 
@@ -3311,6 +3364,7 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
             return DV_ERR_ARG;
     for (uint32_t l = 0; l < n_lanes; l++)
         if (lanes[l]->comm) return DV_ERR_STATE;
+    if (track_check(c0, 2 * n_lanes, n_epochs)) return DV_ERR_ARG;
     HIPCHK(hipSetDevice(c0->cfg.device));
     for (uint32_t l = 0; l < n_lanes; l++) {
         r = carry_bufs(lanes[l], carry_blocks(n_txn));
@@ -3319,7 +3373,13 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     const LoopForm form = loop_form(c0, pool, bufs, 2 * n_lanes, n_txn);
     // lane l's j-th epoch of this call (global k = j * L + l) sits in buffer
     // 2l + (j & 1); its refill writes 2l + ((j + 1) & 1)
-    auto buf_of = [&](uint32_t k, uint32_t ahead) { return &bufs[2 * (k % n_lanes) + (((k / n_lanes) + ahead) & 1)]; };
+    auto buf_i = [&](uint32_t k, uint32_t ahead) { return 2 * (k % n_lanes) + (((k / n_lanes) + ahead) & 1); };
+    auto buf_of = [&](uint32_t k, uint32_t ahead) { return &bufs[buf_i(k, ahead)]; };
+    // (the tracker is lanes[0]'s, shared: the refills run in epoch order)
+    RefillTrack tw;
+    auto track_of = [&](uint32_t k) {
+        return track_at(c0, true, k, k + n_lanes, buf_i(k, 0), buf_i(k, 1), n_lanes, &tw);
+    };
     auto desc = [&](uint32_t k) {
         dv_epoch_dev d = *buf_of(k, 0);
         if (form.old) d.txn_begin = d.recs32 = nullptr;  // (the engine reads the old form)
@@ -3334,7 +3394,8 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     if (!resume)  // each lane's first epoch: fresh txns, drawn in lane order
         for (uint32_t l = 0; l < n_lanes; l++) {
             dv_ctx *c = lanes[l];
-            enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, *buf_of(l, 0), form);
+            enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, *buf_of(l, 0), form,
+                           track_at(c0, false, 0, l, 0, buf_i(l, 0), n_lanes, &tw));
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(c->stream));
         }
@@ -3349,7 +3410,7 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
         },
         [&](dv_ctx *c, uint32_t k) {  // (behind the execution; a no-op when k halted)
             const dv_epoch_dev d = desc(k);
-            enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form);
+            enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form, track_of(k));
             return hip_fail(hipGetLastError(), "refill");
         },
         [&](uint32_t k, dv_stats *st) {  // (synchronous, refill included: the next refill, on
@@ -3358,14 +3419,43 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
             const dv_epoch_dev d = desc(k);
             int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, st);
             if (!e) {
-                enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form);
+                enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form,
+                               track_of(k));
                 e = hip_fail(hipGetLastError(), "refill");
             }
             if (!e) e = hip_fail(hipStreamSynchronize(c->stream), "sync");
             return e;
         });
     for (uint32_t l = 0; l < n_lanes; l++) (void)hipStreamSynchronize(lanes[l]->stream);
+    if (!r && c0->trk.on) c0->trk.next += n_epochs;
     return r;
+}
+
+int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
+    if (!c) return DV_ERR_ARG;
+    if (!trk) {
+        c->trk = dv_ctx::LoopTrk{};
+        return DV_OK;
+    }
+    if (!trk->ids || !trk->n_bufs || (trk->n_bufs & 1) || trk->n_bufs > 2 * kMaxLanes || !trk->log ||
+        !trk->log_cap || !trk->epoch_cap || !trk->log_pos || !trk->epoch_end || !trk->retry_hist || !trk->n_bins ||
+        trk->n_bins > kTrackBins || !trk->totals)
+        return DV_ERR_ARG;
+    for (uint32_t b = 0; b < trk->n_bufs; b++)
+        if (!trk->ids[b]) return DV_ERR_ARG;
+    if (c->phase != 0 || c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
+    if (!c->trk_part) {
+        HIPCHK(hipSetDevice(c->cfg.device));
+        int r = dalloc(&c->trk_part, (uint64_t)kTrackSlots * (kTrackBins + 4));
+        if (r) return r;
+        HIPCHK(hipMemset(c->trk_part, 0, sizeof(uint32_t) * kTrackSlots * (kTrackBins + 4)));
+    }
+    c->trk.on = true;
+    c->trk.t = *trk;
+    c->trk.ids.assign(trk->ids, trk->ids + trk->n_bufs);
+    c->trk.t.ids = nullptr;  // (the caller's array is not kept: ids above)
+    c->trk.next = trk->first_epoch;
+    return DV_OK;
 }
 
 }  // extern "C"

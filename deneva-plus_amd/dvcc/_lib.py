@@ -161,6 +161,13 @@ class WireDevResult(ctypes.Structure):  # dv_wire_dev_result
                 ("max_txn_acc", ctypes.c_uint32), ("n_acc", ctypes.c_uint64), ("next_txn", ctypes.c_uint64)]
 
 
+class LoopTrackDesc(ctypes.Structure):  # dv_loop_track (dv_closed_loop_track; dvcc.LoopTrack owns the arrays)
+    _fields_ = [("ids", ctypes.POINTER(ctypes.c_void_p)), ("n_bufs", ctypes.c_uint32),
+                ("first_epoch", ctypes.c_uint32), ("log", ctypes.c_void_p), ("log_cap", ctypes.c_uint32),
+                ("epoch_cap", ctypes.c_uint32), ("log_pos", ctypes.c_void_p), ("epoch_end", ctypes.c_void_p),
+                ("retry_hist", ctypes.c_void_p), ("n_bins", ctypes.c_uint32), ("totals", ctypes.c_void_p)]
+
+
 # TPC-C table ids and operation words (include/dvcc.h)
 T_WAREHOUSE, T_DISTRICT, T_CUSTOMER, T_ITEM, T_STOCK, T_CUST_LAST = 0, 1, 2, 3, 4, 5
 TOP_NONE, TOP_PAY_WH, TOP_PAY_DIST, TOP_PAY_CUST, TOP_NO_DIST, TOP_NO_STOCK = 0, 1, 2, 3, 4, 5
@@ -265,6 +272,7 @@ SIGNATURES = [
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
+    ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
 ]
 
 _lib = None

@@ -251,6 +251,102 @@ class ClosedLoopBufs:
                                         max_txn_acc=max_txn_acc)
 
 
+class LoopTrack:
+    """A closed loop's tracker (dv_closed_loop_track): the identity words of
+    n_bufs epoch buffers of n_txn txns (2, or 2 per lane), a commit log of
+    log_cap entries, room for epoch_cap epochs, a histogram of retries at
+    commit with n_bins bins (the last one saturating) and the four totals --
+    all device tensors this object owns.  attach() it to an engine and pass it
+    as track= to closed_loop / closed_loop_lanes / TpccEngine.closed_loop (to
+    the engine the loop is called on: the first of the lanes)."""
+
+    def __init__(self, n_txn, n_bufs=2, log_cap=None, epoch_cap=64, n_bins=64, device="cuda"):
+        import torch
+        self.n_txn, self.n_bufs, self.n_bins = int(n_txn), int(n_bufs), int(n_bins)
+        self.epoch_cap = int(epoch_cap)
+        self.log_cap = int(log_cap) if log_cap is not None else self.n_txn * self.epoch_cap
+        z = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=device)  # noqa: E731
+        self.ids = [z(self.n_txn, torch.int64) for _ in range(self.n_bufs)]
+        self.log, self.log_pos = z(self.log_cap, torch.int64), z(1, torch.int32)
+        self.epoch_end = z(self.epoch_cap, torch.int32)
+        self.hist, self.tot = z(self.n_bins, torch.int64), z(4, torch.int64)
+        self.engine, self.first_epoch, self.done, self._off, self._pos0 = None, 0, 0, 0, 0
+
+    def _attach(self):
+        arr = (ctypes.c_void_p * self.n_bufs)(*[int(t.data_ptr()) for t in self.ids])
+        d = L.LoopTrackDesc(arr, self.n_bufs, self.first_epoch + self._off, self.log.data_ptr(), self.log_cap,
+                            self.epoch_cap - self._off, self.log_pos.data_ptr(),
+                            self.epoch_end.data_ptr() + 4 * self._off, self.hist.data_ptr(), self.n_bins,
+                            self.tot.data_ptr())
+        L.check(L.lib().dv_closed_loop_track(self.engine._ctx, ctypes.byref(d)), "dv_closed_loop_track")
+
+    def attach(self, engine, first_epoch=0):
+        """Tracks `engine`'s closed loops from loop epoch first_epoch on.  The
+        tensors stay as they are: attaching again (after drain(), say) with the
+        next epoch's number continues the identities in ids."""
+        if self.engine is not None and self.engine is not engine:
+            self.detach()
+        self.engine, self.first_epoch, self.done, self._off = engine, int(first_epoch), 0, 0
+        self._pos0 = int(self.log_pos.item()) & 0xFFFFFFFF
+        try:
+            self._attach()
+        except Exception:
+            self.engine = None
+            raise
+        engine._track = self
+        return self
+
+    def detach(self):
+        if self.engine is not None:
+            L.check(L.lib().dv_closed_loop_track(self.engine._ctx, None), "dv_closed_loop_track")
+            self.engine._track = None
+            self.engine = None
+
+    def drain(self):
+        """an empty log again (the histogram and the totals run on); attach again after it"""
+        self.log_pos.zero_()
+        self.epoch_end.zero_()
+
+    def swap(self):
+        """with ClosedLoopBufs.swap, after a call of n_epochs odd: the next
+        epoch's identity words move to buffer 0 too"""
+        if self.n_bufs != 2:
+            raise ValueError("LoopTrack.swap: a single loop's two buffers only")
+        self.ids.reverse()
+        self._off = self.done
+        if self.engine is not None and self._off < self.epoch_cap:  # (no epochs left: attach() comes next)
+            self._attach()
+
+    def _before(self, engine, n_txn, n_bufs):
+        if self.engine is not engine:
+            raise ValueError("track= names a LoopTrack that is not attached to this engine")
+        if n_txn > self.n_txn or n_bufs != self.n_bufs:
+            raise ValueError(f"LoopTrack of {self.n_bufs} x {self.n_txn} txns in a loop of {n_bufs} x {n_txn}")
+
+    def ends(self):
+        """the commit count after each epoch run since attach (numpy, uint32)"""
+        return self.epoch_end[:self.done].cpu().numpy().view(np.uint32).copy()
+
+    def commits(self, i):
+        """(src, born) of the txns committed in the i-th epoch since attach, in
+        sequence order (int64 device tensors; what fitted below log_cap)"""
+        e = self.ends()
+        lo, hi = (int(e[i - 1]) if i else self._pos0), int(e[i])
+        w = self.log[min(lo, self.log_cap):min(hi, self.log_cap)]
+        return w & 0xFFFFFFFF, w >> 32
+
+    def histogram(self):
+        return self.hist.cpu().numpy().copy()
+
+    def totals(self):
+        """committed, aborted, first aborts, most retries at a commit"""
+        return [int(v) for v in self.tot.cpu().numpy()]
+
+    def overflowed(self):
+        """commits counted past log_cap (not written)"""
+        return max(0, (int(self.log_pos.item()) & 0xFFFFFFFF) - self.log_cap)
+
+
 def _loop_tb(pool, bufs):
     """dv_epoch_run_closed_loop writes the tb form (loop_tb, dvcc_runtime.hip)"""
     import os
@@ -332,7 +428,8 @@ class CCEngine:
         configuration over this engine's tables (loaded first; frozen while
         lanes are open).  Closed with, or before, this engine."""
         lane = type(self).__new__(type(self))
-        lane.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_ctx", "_lanes", "_ev", "_ext")})
+        own = ("_ctx", "_lanes", "_ev", "_ext", "_track")
+        lane.__dict__.update({k: v for k, v in self.__dict__.items() if k not in own})
         lane._ctx = ctypes.c_void_p()
         L.check(L.lib().dv_open_lane(self._ctx, ctypes.byref(lane._ctx)), "dv_open_lane")
         lane._owner, lane._lanes = self, []
@@ -712,16 +809,27 @@ class CCEngine:
                 L.lib().dv_comm_set_mode(self._ctx, prev)
         return list(sts)
 
+    def _tracked(self, track, n_txn, n_bufs):
+        """the LoopTrack a loop call on this engine runs under (track=, or the
+        one attached), checked against the call"""
+        track = track if track is not None else getattr(self, "_track", None)
+        if track is not None:
+            track._before(self, n_txn, n_bufs)
+        return track
+
     def closed_loop(self, pool, pool_begin, n_txn, n_epochs, cursor=None, bufs=None, d_commits=None,
-                    resume=False):
+                    resume=False, track=None):
         """The closed loop on the device (dv_epoch_run_closed_loop): n_epochs
         epochs of n_txn txns, each the previous one's aborted txns then fresh
         ones from `pool` (a DeviceEpoch with max_txn_acc > 0; pool_begin: its
         n_txn + 1 access offsets, int32 device tensor) from the device word
         `cursor` (int32 tensor, advanced).  bufs: ClosedLoopBufs (allocated when
-        None); d_commits: a device tensor per epoch (or None).  Returns (stats
-        list, bufs, cursor); the next epoch is in bufs.epoch(n_epochs & 1)."""
+        None); d_commits: a device tensor per epoch (or None).  track: a LoopTrack
+        attached to this engine (identity through the loop: its commit log,
+        retry histogram and totals).  Returns (stats list, bufs, cursor); the
+        next epoch is in bufs.epoch(n_epochs & 1)."""
         import torch
+        track = self._tracked(track, n_txn, 2)
         dev = pool.keys.device
         if cursor is None:
             cursor = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -738,19 +846,23 @@ class CCEngine:
         L.check(L.lib().dv_epoch_run_closed_loop(self._ctx, ctypes.byref(pool.desc()), _ptr(pool_begin),
                                                  _ptr(cursor), n_txn, arr, bufs.cap, n_epochs, int(resume),
                                                  cps, sts), "dv_epoch_run_closed_loop")
+        if track is not None:
+            track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor
 
     def closed_loop_lanes(self, lanes, pool, pool_begin, n_txn, n_epochs, cursor=None, bufs=None,
-                          d_commits=None, resume=False):
+                          d_commits=None, resume=False, track=None):
         """dv_epoch_run_closed_loop_lanes over [self] + lanes: epoch k on
         context k % L, each context's epochs a closed loop of their own
         (aborted txns retried L epochs later), the pool cursor shared.  bufs:
-        one ClosedLoopBufs per context (allocated when None).  Returns (stats
+        one ClosedLoopBufs per context (allocated when None).  track: a
+        LoopTrack of 2 L buffers attached to this engine.  Returns (stats
         list, bufs, cursor); resume needs the previous call's n_epochs to be a
         multiple of 2 L."""
         import torch
         ctxs = [self] + list(lanes)
         nl = len(ctxs)
+        track = self._tracked(track, n_txn, 2 * nl)
         dev = pool.keys.device
         if cursor is None:
             cursor = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -772,6 +884,8 @@ class CCEngine:
         L.check(L.lib().dv_epoch_run_closed_loop_lanes(lp, nl, ctypes.byref(pool.desc()), _ptr(pool_begin),
                                                        _ptr(cursor), n_txn, arr, bufs[0].cap, n_epochs,
                                                        int(resume), cps, sts), "dv_epoch_run_closed_loop_lanes")
+        if track is not None:
+            track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor
 
     def group_carry(self, homes, d_commit, txns_per_rank, max_txn=None):

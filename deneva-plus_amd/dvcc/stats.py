@@ -7,6 +7,11 @@ scripts/helper.py (get_summary / process_results, helper.py:755-815, 934-944)
 parses engine runs like rundb output.  Times are seconds, as the reference
 prints them (x / BILLION).  Counters of subsystems outside this path
 (network, queues, latency breakdowns) are not printed.
+
+`summary_fields` sees only per-epoch counts, where an abort is an abort.  A
+closed loop run with a tracker (dvcc.LoopTrack) knows each txn through its
+retries: `retry_summary_fields` prints the same keys with Deneva's distinction
+between total and unique aborts and with latencies that include the retries.
 """
 
 
@@ -66,4 +71,39 @@ def summary_fields(total_runtime_s, stats, multi_part_txn_cnt=0, parts_touched=N
 def summary_line(total_runtime_s, stats, prog=False, **kw):
     body = ",".join(f"{k}={v:f}" if isinstance(v, float) else f"{k}={v:d}"
                     for k, v in summary_fields(total_runtime_s, stats, **kw))
+    return ("[prog] " if prog else "[summary] ") + body
+
+
+def retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, epoch_seconds=None, **kw):
+    """summary_fields for a closed loop run under a loop tracker: the same keys,
+    with what the tracker knows about retries.  totals / hist: LoopTrack.totals()
+    (committed, aborted, first aborts, max retries) and LoopTrack.histogram()
+    over the epochs of `stats`; penalty_epochs: epochs until an aborted txn runs
+    again (1, or the lanes loop's lane count).
+    unique_txn_abort_cnt is the first aborts: a txn aborted five times counts
+    five in total_txn_abort_cnt and one here, as Stats_thd counts them
+    (txn.cpp: unique_txn_abort_cnt only when the txn had not aborted before).
+    txn_run_time charges a commit after r retries r * penalty_epochs + 1
+    epochs of the mean epoch time (epoch_seconds' mean when given, else the
+    run's share), from the histogram -- exact while no commit lands in its last,
+    saturating bin (every commit there is charged n_bins - 1 retries: a lower
+    bound); txn_run_avg_time divides by the commits."""
+    base = dict(summary_fields(total_runtime_s, stats, epoch_seconds=epoch_seconds, **kw))
+    hist = [int(h) for h in hist]
+    n_ep = len(stats)
+    if epoch_seconds is not None and len(epoch_seconds):
+        per = sum(float(e) for e in epoch_seconds) / len(epoch_seconds)
+    else:
+        per = float(total_runtime_s) / n_ep if n_ep else 0.0
+    run_time = sum(h * (r * int(penalty_epochs) + 1) for r, h in enumerate(hist)) * per
+    commits = sum(hist)
+    base["unique_txn_abort_cnt"] = int(totals[2])
+    base["txn_run_time"] = run_time
+    base["txn_run_avg_time"] = run_time / commits if commits else 0.0
+    return list(base.items())
+
+
+def retry_summary_line(total_runtime_s, stats, totals, hist, penalty_epochs, prog=False, **kw):
+    body = ",".join(f"{k}={v:f}" if isinstance(v, float) else f"{k}={v:d}"
+                    for k, v in retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, **kw))
     return ("[prog] " if prog else "[summary] ") + body

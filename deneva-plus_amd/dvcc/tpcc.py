@@ -170,7 +170,7 @@ class TpccEngine(CCEngine):
                                          max_txn_acc=int(out.max_txn_acc)), args[:n])
 
     def closed_loop(self, pool, pool_args, pool_begin, n_txn, n_epochs, cursor=None, bufs=None, d_commits=None,
-                    d_oids=None, resume=False):
+                    d_oids=None, resume=False, track=None):
         """The TPC-C closed loop on the device (dv_tpcc_epoch_run_closed_loop):
         n_epochs epochs of n_txn txns, each the previous one's aborted txns
         (with their operation words) then fresh ones from `pool` (a DeviceEpoch
@@ -178,9 +178,11 @@ class TpccEngine(CCEngine):
         pool_begin: its n_txn + 1 access offsets, int32 device tensor) from the
         device word `cursor` (int32 tensor, advanced).  bufs: TpccLoopBufs
         (allocated when None); d_commits / d_oids: a device tensor per epoch,
-        one for all, or None.  Returns (stats list, bufs, cursor); the next
-        epoch is in bufs.epoch(n_epochs & 1)."""
+        one for all, or None.  track: a LoopTrack attached to this engine.
+        Returns (stats list, bufs, cursor); the next epoch is in
+        bufs.epoch(n_epochs & 1)."""
         import torch
+        track = self._tracked(track, n_txn, 2)
         dev = pool.keys.device
         if cursor is None:
             cursor = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -197,6 +199,8 @@ class TpccEngine(CCEngine):
                                                       n_epochs, int(resume), _commit_ptrs(d_commits, n),
                                                       _commit_ptrs(d_oids, n), sts),
                 "dv_tpcc_epoch_run_closed_loop")
+        if track is not None:
+            track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor
 
     def run_tpcc_epoch_part(self, home, d_args, d_owner, txns_per_rank, d_commit, d_oid=None):

@@ -255,7 +255,11 @@ class DeviceWireIngress:
                                                     ep.client_startts.data_ptr(), ep.return_node.data_ptr(),
                                                     tid.data_ptr(), cst.data_ptr(), rn.data_ptr(),
                                                     ctypes.byref(cnt)), "dv_wire_reply_fields_device")
-        c = cnt.value
+        return self._pack(tid, cst, rn, cnt.value)
+
+    def _pack(self, tid, cst, rn, c):
+        """the host packer (dv_wire_respond) over the first c entries of device
+        reply fields, every one committed"""
         if not c:
             return []
         e = L.WireEpoch()
@@ -272,6 +276,21 @@ class DeviceWireIngress:
         L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
                                         _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
         return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
+
+    def respond_logged(self, src):
+        """The CL_RSP batches (bytes) of the pool txns `src` names: a slice of
+        a closed loop's commit log (LoopTrack.commits(i)[0], an integer device
+        tensor of indices into the epoch this ingress decoded last, which the
+        loop ran as its pool).  Their reply fields are gathered by index on the
+        device, then packed as respond packs its compacted ones -- a server
+        answering at commit, whatever epoch a txn committed in."""
+        import torch
+        idx = src.to(device=self.txn_id.device, dtype=torch.int64)
+        c = int(idx.numel())
+        if not c:
+            return []
+        self.engine._after_torch()
+        return self._pack(self.txn_id[idx], self.client_startts[idx], self.return_node[idx], c)
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

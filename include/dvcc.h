@@ -516,6 +516,72 @@ int dv_epoch_run_closed_loop(dv_ctx *ctx, const dv_epoch_dev *pool, const uint32
                              uint32_t n_txn, dv_epoch_dev *bufs, uint64_t buf_cap, uint32_t n_epochs, int resume,
                              uint8_t *const *d_commits, dv_stats *sts);
 
+/* Identity through the closed loop: an optional tracker attached to a context.
+ * The loop renumbers the carried txns from 0 in every refill; with a tracker
+ * every refill of a closed loop on that context (dv_epoch_run_closed_loop,
+ * dv_epoch_run_closed_loop_lanes, dv_tpcc_epoch_run_closed_loop) also, on the
+ * device and in epoch order,
+ *   1. moves one identity word per txn with the carried txns and gives every
+ *      fresh txn a new one: src | born << 32 -- src the txn's index in the
+ *      pool ((cursor + f) % pool->n_txn for the refill's f-th fresh txn), born
+ *      the loop epoch number of the epoch it first ran in (a pool that wraps
+ *      yields the same src with a later born);
+ *   2. appends the identity words of the epoch's committed txns, in sequence
+ *      order, to a commit log;
+ *   3. adds them to a histogram of retries at commit -- (k - born) / L for a
+ *      commit in epoch k, L = 1, or n_lanes for the lanes loop (a txn returns L
+ *      epochs later, so the division is exact) -- and to four running totals.
+ * Without a tracker the loops launch exactly what they launched before.
+ *   ids[i]: the identity words of the epoch in the loop's bufs[i] (the same
+ *     indexing: 2 arrays, or 2 * n_lanes with lane l's pair at 2l, 2l + 1),
+ *     each at least the loop's n_txn words.  A caller that swaps bufs[0] and
+ *     bufs[1] to resume after an odd n_epochs attaches again with the ids
+ *     arrays swapped too (and first_epoch, epoch_end, epoch_cap moved on by the
+ *     epochs run; dvcc.LoopTrack.swap does it).
+ *   first_epoch: the loop epoch number of the first epoch run after attaching;
+ *     the counter runs on across calls (resume or not).  Attaching again with
+ *     the same ids arrays and the next epoch's number continues the identities
+ *     with whatever log the new struct names (e.g. the same one, *log_pos set
+ *     to 0 by the caller: a drained log).
+ *   log / log_pos / epoch_end: the log's entries [epoch_end[i - 1], epoch_end[i])
+ *     (*log_pos at attach time for i = 0) are epoch first_epoch + i's commits.
+ *     Log overflow is counted, not written: entries at positions >= log_cap
+ *     are dropped, nothing is stored at or past log + log_cap, and *log_pos and
+ *     epoch_end keep the true counts.
+ *   retry_hist[n_bins] (n_bins <= 1024), added to: bin min(retries, n_bins - 1).
+ *   totals[4], added to: committed, aborted (one per abort), first aborts
+ *     (aborted in the epoch they were born in: Deneva's unique_txn_abort_cnt),
+ *     and the most retries any commit took (a maximum, not a sum).
+ * Attaching touches no device memory: the caller initialises *log_pos, the
+ * histogram and the totals.  The struct and the ids pointers are copied; the
+ * tracker belongs to the context the loop is called on (lanes[0] for the lanes
+ * loop: the lanes share it).  NULL detaches.
+ * Refused at attach time: a null context, array or ids entry, n_bufs, log_cap,
+ * epoch_cap or n_bins of 0, n_bufs odd or above 16, n_bins above 1024
+ * (DV_ERR_ARG); a CALVIN context or one with a communicator (DV_ERR_STATE, as
+ * the loops themselves; CALVIN never aborts).  A loop call whose buffer count
+ * (2, or 2 * n_lanes) is not n_bufs, or whose n_epochs exceeds what is left of
+ * epoch_cap, returns DV_ERR_ARG before any launch.
+ * A refill behind a halted or failed epoch is a no-op, and so is its tracker
+ * pass (the same device word decides both); the host decides that epoch again
+ * and queues the refill again, so every epoch is logged exactly once.  The
+ * tracker's launches (k_track_carry, k_track_fresh) follow the refill's,
+ * outside any captured epoch graph. */
+typedef struct dv_loop_track {
+    uint64_t *const *ids;   /* [n_bufs] device arrays of identity words                  */
+    uint32_t n_bufs;
+    uint32_t first_epoch;
+    uint64_t *log;          /* device [log_cap]                                           */
+    uint32_t log_cap;
+    uint32_t epoch_cap;     /* epochs this attachment may run                             */
+    uint32_t *log_pos;      /* device word, in/out: the running commit count              */
+    uint32_t *epoch_end;    /* device [epoch_cap]: *log_pos after epoch first_epoch + i   */
+    uint64_t *retry_hist;   /* device [n_bins]                                            */
+    uint32_t n_bins;
+    uint64_t *totals;       /* device [4]                                                 */
+} dv_loop_track;
+int dv_closed_loop_track(dv_ctx *ctx, const dv_loop_track *trk);
+
 /* Epoch groups -- epoch-parallel scheduling for YCSB: a
  * group is P = nranks consecutive epochs of the sequencer, and homes[e]
  * (n_homes == P) is this rank's client batch of epoch e (txn ids local,
