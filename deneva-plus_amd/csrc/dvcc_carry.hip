@@ -402,18 +402,10 @@ __global__ __launch_bounds__(kBlock) void k_track_carry(const uint8_t *__restric
     if (blockIdx.x == 0 && tid == 0) *tr.epoch_end = pos0 + (n_txn - tot[2]);
 }
 
-// the F fresh txns' identity words behind the C carried ones: their pool index
-// and the number of the epoch being built; and (prev: there was an epoch to
-// log) what k_track_carry left -- the commit count, and the kTrackSlots copies
-// of the histogram and the counts, added to the caller's (one thread a word:
-// plain 8-byte stores) and cleared for the next refill
-__global__ __launch_bounds__(kBlock) void k_track_fresh(const uint32_t *__restrict__ tot, uint32_t n_out,
-                                                        uint32_t pool_n, int prev, RefillTrack tr) {
-    if (tot[4]) return;
-    const uint32_t C = tot[2] < n_out ? tot[2] : n_out, cur = tot[3], F = tot[5];
-    for (uint32_t f = blockIdx.x * kBlock + threadIdx.x; f < F && C + f < n_out; f += gridDim.x * kBlock)
-        tr.oids[C + f] = (((uint64_t)cur + f) % pool_n) | (uint64_t)tr.k_next << 32;
-    if (!prev) return;
+// what k_track_carry (or k_bo_park) left -- the commit count, and the
+// kTrackSlots copies of the histogram and the counts, added to the caller's
+// (one thread a word: plain 8-byte stores) and cleared for the next refill
+__device__ __forceinline__ void track_fold(const RefillTrack &tr) {
     const uint32_t stride = tr.n_bins + 4;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < stride; i += gridDim.x * kBlock) {
         const bool is_max = i == tr.n_bins + 3;
@@ -430,6 +422,18 @@ __global__ __launch_bounds__(kBlock) void k_track_fresh(const uint32_t *__restri
         *w = is_max ? (*w > sum ? *w : (uint64_t)sum) : *w + sum;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *tr.log_pos = *tr.epoch_end;
+}
+
+// the F fresh txns' identity words behind the C carried ones: their pool index
+// and the number of the epoch being built; and (prev: there was an epoch to
+// log) the fold above
+__global__ __launch_bounds__(kBlock) void k_track_fresh(const uint32_t *__restrict__ tot, uint32_t n_out,
+                                                        uint32_t pool_n, int prev, RefillTrack tr) {
+    if (tot[4]) return;
+    const uint32_t C = tot[2] < n_out ? tot[2] : n_out, cur = tot[3], F = tot[5];
+    for (uint32_t f = blockIdx.x * kBlock + threadIdx.x; f < F && C + f < n_out; f += gridDim.x * kBlock)
+        tr.oids[C + f] = (((uint64_t)cur + f) % pool_n) | (uint64_t)tr.k_next << 32;
+    if (prev) track_fold(tr);
 }
 
 void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
@@ -468,6 +472,390 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
     const uint32_t gf = (n_out + kBlock - 1) / kBlock;
     DV_LAUNCH(k_track_fresh, gf < 1 ? 1 : (gf > 1024 ? 1024 : gf), kBlock, 0, s, tot, n_out, pool_n, nb ? 1 : 0,
               *trk);
+}
+
+// ---- back-off (dv_closed_loop_backoff): the reference's AbortQueue::enqueue
+// meant penalty * 2^abort_cnt capped at a maximum (abort_queue.cpp:26-31;
+// written with ^ as XOR and max for min).  Here the penalty is
+// counted in epochs: a txn's a-th abort parks it min(2^(a-1), D) epochs ahead
+// in a ring of D slots, slot e % D holding what falls due in epoch e.  A
+// parked txn is its identity word and an abort count byte (9 bytes); its
+// accesses are read from the pool again when it is released.  The chain behind
+// epoch k (building epoch e = k + 1, all kernel boundaries, no flags):
+//   k_bo_count   per 256-txn carry block and delay class, the aborts
+//   k_bo_scan    a workgroup per class: exclusive scan over the blocks
+//   k_bo_plan    one thread: the skip word; per class its slot and the slot's
+//                count before (the scatter's base), the counts after; the
+//                release R = min(count[e % D], n_out), the spill behind it
+//                (to the tail of slot (e + 1) % D), F = n_out - R, the cursor
+//   k_bo_park    the scatter (base + block prefix + rank within the class, in
+//                sequence order) and the tracker's pass over the commits
+//   k_bo_spill   the spill's words and bytes to the next slot's tail
+//   k_bo_gather_count / k_bo_scan / k_bo_gather_copy   the new epoch: src from
+//                the slot (j < R) or the cursor range, length from pool_begin,
+//                the accesses streamed from the pool
+//   k_bo_fold    the tracker's fold (track_fold) and the wait sum
+// Positions at or past the slots' capacity are counted (lost) and not written.
+// bw[]: the plan words
+enum : uint32_t {
+    BW_CTOT = 0,    // [kBoClasses] aborts per class
+    BW_BASE = 5,    // [kBoClasses] the class's slot count before the park
+    BW_SLOT = 10,   // [kBoClasses] the class's slot
+    BW_SRC = 15,    // the slot released
+    BW_DST = 16,    // the slot taking the spill
+    BW_TAIL = 17,   // ... its count before the spill
+    BW_SPILL = 18,  // spill entries written
+    BW_GTOT = 19,   // the new epoch's accesses
+};
+static_assert(BW_GTOT < kBoWords, "plan words");
+
+// the delay class of an abort whose txn had aborted `ab` times before:
+// delay min(2^ab, D)
+__device__ __forceinline__ uint32_t bo_class(uint32_t ab, uint32_t lgD) { return ab < lgD ? ab : lgD; }
+
+__global__ __launch_bounds__(kBlock) void k_bo_count(const uint8_t *__restrict__ status,
+                                                     const uint8_t *__restrict__ aborts, uint32_t n_txn,
+                                                     uint32_t nb, uint32_t lgD, uint32_t *__restrict__ cls) {
+    __shared__ uint32_t s_c[kBoClasses];
+    if (threadIdx.x < kBoClasses) s_c[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t t = blockIdx.x * kCarryTpb + threadIdx.x;
+    const bool cr = t < n_txn && carried(status, t);
+    const uint32_t ci = cr ? bo_class(aborts[t], lgD) : kBoClasses;
+#pragma unroll
+    for (uint32_t c = 0; c < kBoClasses; c++) {
+        const uint64_t m = __ballot(ci == c);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_c[c], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x <= lgD) cls[threadIdx.x * nb + blockIdx.x] = s_c[threadIdx.x];
+}
+
+// workgroup r: exclusive scan of row r of c (n words a row) in place, the
+// row's total into totals[r] (n <= 4,096: a thread's chunk in registers, as
+// k_carry_scan)
+__global__ __launch_bounds__(kBlock) void k_bo_scan(uint32_t *__restrict__ c, uint32_t n,
+                                                    uint32_t *__restrict__ totals) {
+    __shared__ uint32_t lds4[4];
+    uint32_t *const row = c + (size_t)blockIdx.x * n;
+    const uint32_t per = (n + kBlock - 1) / kBlock;
+    const uint32_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+    constexpr uint32_t kR = 16;
+    uint32_t tot = 0;
+    if (per <= kR) {
+        uint32_t v[kR], sum = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kR; k++) v[k] = k < per && lo + k < n ? row[lo + k] : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < kR; k++) sum += v[k];
+        uint32_t pre = block_excl_scan256(sum, lds4, &tot);
+#pragma unroll
+        for (uint32_t k = 0; k < kR; k++) {
+            if (k < per && lo + k < n) row[lo + k] = pre;
+            pre += v[k];
+        }
+    } else {
+        uint32_t sum = 0;
+        for (uint32_t i = lo; i < hi; i++) sum += row[i];
+        uint32_t pre = block_excl_scan256(sum, lds4, &tot);
+        for (uint32_t i = lo; i < hi; i++) {
+            const uint32_t x = row[i];
+            row[i] = pre;
+            pre += x;
+        }
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = tot;
+}
+
+// k: the epoch decided (prev: there is one), e: the epoch being built
+__global__ void k_bo_plan(int prev, uint32_t k, uint32_t e, uint32_t n_out, uint32_t *cursor, uint32_t pool_n,
+                          const Counters *ctr, uint32_t *tot, RefillBackoff bo) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t skip = prev && refill_skip(ctr) ? 1u : 0u;
+    tot[4] = skip;
+    if (skip) return;
+    const uint32_t mask = bo.D - 1;
+    uint32_t aborted = 0;
+    uint64_t lost = 0;
+    for (uint32_t c = 0; prev && c <= bo.lgD; c++) {  // (the delays 1 .. D fall into distinct slots)
+        const uint32_t slot = (k + (1u << c)) & mask, n = bo.bw[BW_CTOT + c];
+        const uint32_t base = bo.slot_count[slot] < bo.cap ? bo.slot_count[slot] : bo.cap;
+        const uint64_t want = (uint64_t)base + n;
+        const uint32_t now = want < bo.cap ? (uint32_t)want : bo.cap;
+        bo.bw[BW_BASE + c] = base;
+        bo.bw[BW_SLOT + c] = slot;
+        bo.slot_count[slot] = now;
+        lost += want - now;
+        aborted += n;
+    }
+    const uint32_t s = e & mask, s2 = (e + 1) & mask;
+    const uint32_t cnt = bo.slot_count[s] < bo.cap ? bo.slot_count[s] : bo.cap;
+    const uint32_t R = cnt < n_out ? cnt : n_out, sp = cnt - R;
+    uint32_t tail = 0, moved = 0;
+    bo.slot_count[s] = 0;
+    if (s2 != s) {
+        tail = bo.slot_count[s2] < bo.cap ? bo.slot_count[s2] : bo.cap;
+        moved = sp < bo.cap - tail ? sp : bo.cap - tail;
+        bo.slot_count[s2] = tail + moved;
+    }
+    lost += sp - moved;  // (D = 1 never spills: at most n_out txns abort)
+    const uint32_t F = n_out - R, cur = *cursor;
+    *cursor = (uint32_t)(((uint64_t)cur + F) % pool_n);
+    bo.bw[BW_SRC] = s;
+    bo.bw[BW_DST] = s2;
+    bo.bw[BW_TAIL] = tail;
+    bo.bw[BW_SPILL] = moved;
+    tot[0] = R;
+    tot[1] = sp;
+    tot[2] = aborted;
+    tot[3] = cur;
+    tot[5] = F;
+    uint64_t parked = 0;
+    for (uint32_t i = 0; i < bo.D; i++) parked += bo.slot_count[i];
+    bo.counters[0] += sp;
+    bo.counters[1] += lost;
+    bo.counters[3] = parked;
+    *bo.lost += lost;
+}
+
+// k_track_carry's pass with the ring in place of the next epoch: a wave takes
+// one 256-txn carry block, a lane four consecutive txns.  An aborted txn goes
+// to its class's slot at the slot's count before (bw) + the aborts of its
+// class in the blocks before (cls) + its rank in its class in the block -- a
+// wave scan of the lanes' class counts, ten bits a class, three classes to a
+// word.  A committed txn is logged as k_track_carry logs it; the histogram
+// bins it by its abort count, and (k - born), the epochs it took, is summed
+// into one of kTrackSlots 8-byte copies (k_bo_fold adds them up).
+__global__ __launch_bounds__(kBlock) void k_bo_park(const uint8_t *__restrict__ status, uint32_t n_txn,
+                                                    uint32_t nb, const uint32_t *__restrict__ tot, RefillTrack tr,
+                                                    RefillBackoff bo) {
+    __shared__ uint32_t s_hist[kTrackBins];
+    __shared__ uint32_t s_tot[4];  // committed, aborted, first aborts, most aborts at a commit
+    __shared__ unsigned long long s_wait;
+    if (tot[4]) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t i = tid; i < tr.n_bins; i += kBlock) s_hist[i] = 0;
+    if (tid < 4) s_tot[tid] = 0;
+    if (tid == 0) s_wait = 0;
+    __syncthreads();
+    const uint32_t b = blockIdx.x * (kBlock / 64) + wave;  // the wave's carry block (past the last: idle)
+    const bool live = b < nb;
+    const uint64_t t0 = (uint64_t)b * kCarryTpb + lane * kTrackPer;
+    const uint32_t nv = !live || t0 >= n_txn ? 0u : (n_txn - t0 < kTrackPer ? (uint32_t)(n_txn - t0) : kTrackPer);
+    uint64_t word[kTrackPer];
+    uint32_t ab[kTrackPer];
+    bool cr[kTrackPer];
+    uint32_t c = 0, c012 = 0, c34 = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kTrackPer; j++) {
+        word[j] = j < nv ? tr.ids[t0 + j] : 0;
+        ab[j] = j < nv ? bo.aborts[t0 + j] : 0u;
+        cr[j] = j < nv && carried(status, (uint32_t)(t0 + j));
+        if (!cr[j]) continue;
+        const uint32_t ci = bo_class(ab[j], bo.lgD);
+        c++;
+        if (ci < 3) c012 += 1u << (10 * ci);
+        else c34 += 1u << (10 * (ci - 3));
+    }
+    const uint32_t r012 = wave_incl_sum(c012, lane) - c012, r34 = wave_incl_sum(c34, lane) - c34;
+    // per class: where the block's aborts of that class start in their slot
+    uint32_t at[kBoClasses], rank[kBoClasses], before = 0;
+#pragma unroll
+    for (uint32_t ci = 0; ci < kBoClasses; ci++) {
+        const uint32_t pre = live && ci <= bo.lgD ? bo.cls[ci * nb + b] : 0u;
+        at[ci] = ci <= bo.lgD ? bo.bw[BW_BASE + ci] + pre : 0u;
+        rank[ci] = ((ci < 3 ? r012 >> (10 * (ci % 3)) : r34 >> (10 * (ci % 3))) & 1023u);
+        before += pre;
+    }
+    uint32_t r = before + wave_incl_sum(c, lane) - c;  // txns aborted before this lane's first, in the whole epoch
+    const uint32_t pos0 = *tr.log_pos;
+    uint32_t n_cm = 0, n_first = 0, mx = 0;
+    unsigned long long wait = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kTrackPer; j++) {
+        if (j >= nv) continue;
+        const uint32_t born = (uint32_t)(word[j] >> 32);
+        if (cr[j]) {
+            const uint32_t ci = bo_class(ab[j], bo.lgD);
+            uint32_t p = 0, slot = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < kBoClasses; q++)
+                if (q == ci) {
+                    p = at[q] + rank[q];
+                    rank[q]++;
+                    slot = bo.bw[BW_SLOT + q];
+                }
+            if (p < bo.cap) {
+                bo.park_ids[(size_t)slot * bo.cap + p] = word[j];
+                bo.park_aborts[(size_t)slot * bo.cap + p] = (uint8_t)(ab[j] < 255 ? ab[j] + 1 : 255);
+            }
+            r++;
+            n_first += ab[j] == 0 ? 1u : 0u;
+            continue;
+        }
+        const uint64_t pos = (uint64_t)pos0 + ((uint32_t)(t0 + j) - r);
+        if (pos < tr.log_cap) tr.log[pos] = word[j];
+        atomicAdd(&s_hist[ab[j] < tr.n_bins - 1 ? ab[j] : tr.n_bins - 1], 1u);
+        mx = ab[j] > mx ? ab[j] : mx;
+        wait += tr.k - born;
+        n_cm++;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n_cm += __shfl_xor(n_cm, off, 64);
+        c += __shfl_xor(c, off, 64);
+        n_first += __shfl_xor(n_first, off, 64);
+        const uint32_t o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+        wait += __shfl_xor(wait, off, 64);
+    }
+    if (lane == 0) {
+        if (n_cm) atomicAdd(&s_tot[0], n_cm);
+        if (c) atomicAdd(&s_tot[1], c);
+        if (n_first) atomicAdd(&s_tot[2], n_first);
+        if (mx) atomicMax(&s_tot[3], mx);
+        if (wait) atomicAdd(&s_wait, wait);
+    }
+    __syncthreads();
+    uint32_t *const part = tr.part + (size_t)(blockIdx.x % kTrackSlots) * (tr.n_bins + 4);
+    for (uint32_t i = tid; i < tr.n_bins; i += kBlock)
+        if (s_hist[i]) atomicAdd(&part[i], s_hist[i]);
+    if (tid < 3 && s_tot[tid]) atomicAdd(&part[tr.n_bins + tid], s_tot[tid]);
+    if (tid == 3 && s_tot[3]) atomicMax(&part[tr.n_bins + 3], s_tot[3]);
+    if (tid == 4 && s_wait) atomicAdd(&bo.wpart[blockIdx.x % kTrackSlots], s_wait);
+    if (blockIdx.x == 0 && tid == 0) *tr.epoch_end = pos0 + (n_txn - tot[2]);
+}
+
+// the released slot's entries behind the first R, to the next slot's tail
+__global__ __launch_bounds__(kBlock) void k_bo_spill(const uint32_t *__restrict__ tot, RefillBackoff bo) {
+    if (tot[4]) return;
+    const uint32_t n = bo.bw[BW_SPILL];
+    const size_t from = (size_t)bo.bw[BW_SRC] * bo.cap + tot[0], to = (size_t)bo.bw[BW_DST] * bo.cap + bo.bw[BW_TAIL];
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        bo.park_ids[to + i] = bo.park_ids[from + i];
+        bo.park_aborts[to + i] = bo.park_aborts[from + i];
+    }
+}
+
+// the new epoch's txn j: the released slot's j-th entry, or the (j - R)-th
+// fresh pool txn; its identity word and abort count, and per block the
+// accesses (a src outside the pool -- a ring the caller filled -- has none)
+__global__ __launch_bounds__(kBlock) void k_bo_gather_count(const uint32_t *__restrict__ tot, uint32_t n_out,
+                                                            const uint32_t *__restrict__ ptb, uint32_t pool_n,
+                                                            uint64_t *__restrict__ oids, uint32_t k_next,
+                                                            RefillBackoff bo) {
+    __shared__ uint32_t lds4[4];
+    if (tot[4]) return;
+    const uint32_t j = blockIdx.x * kCarryTpb + threadIdx.x, R = tot[0], cur = tot[3];
+    uint32_t len = 0;
+    if (j < n_out) {
+        uint64_t w;
+        uint8_t a = 0;
+        if (j < R) {
+            const size_t p = (size_t)bo.bw[BW_SRC] * bo.cap + j;
+            w = bo.park_ids[p];
+            a = bo.park_aborts[p];
+        } else {
+            w = (((uint64_t)cur + (j - R)) % pool_n) | (uint64_t)k_next << 32;
+        }
+        const uint32_t src = (uint32_t)w;
+        len = src < pool_n ? ptb[src + 1] - ptb[src] : 0u;
+        oids[j] = w;
+        bo.oaborts[j] = a;
+    }
+    uint32_t total = 0;
+    (void)block_excl_scan256(len, lds4, &total);
+    if (threadIdx.x == 0) bo.gb[blockIdx.x] = total;
+}
+
+// every txn's boundary, then the block streams its txns' accesses from the
+// pool: an access's txn by a binary search over the block's output starts in
+// LDS (non-decreasing: an exclusive scan), as k_carry_copy
+__global__ __launch_bounds__(kBlock) void k_bo_gather_copy(
+    const uint32_t *__restrict__ tot, uint32_t n_out, const uint64_t *__restrict__ oids,
+    const uint64_t *__restrict__ pkeys, const uint8_t *__restrict__ ptypes, const uint8_t *__restrict__ ptables,
+    const uint32_t *__restrict__ ptb, uint32_t pool_n, const uint32_t *__restrict__ precs,
+    uint64_t *__restrict__ okeys, uint8_t *__restrict__ otypes, uint32_t *__restrict__ otxn,
+    uint8_t *__restrict__ otables, uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb,
+    uint32_t *__restrict__ n_acc_dev, uint64_t acc_cap, RefillBackoff bo) {
+    __shared__ uint32_t lds4[4];
+    __shared__ uint32_t s_st[kCarryTpb], s_p0[kCarryTpb];
+    if (tot[4]) return;
+    const uint32_t tid = threadIdx.x, j = blockIdx.x * kCarryTpb + tid;
+    uint32_t p0 = 0, len = 0;
+    if (j < n_out) {
+        const uint32_t src = (uint32_t)oids[j];
+        if (src < pool_n) {
+            p0 = ptb[src];
+            len = ptb[src + 1] - p0;
+        }
+    }
+    uint32_t btot = 0;
+    const uint32_t st = block_excl_scan256(len, lds4, &btot), base = bo.gb[blockIdx.x];
+    if (j < n_out && otb) otb[j] = base + st;
+    if (blockIdx.x == 0 && tid == 0) {
+        *n_acc_dev = bo.bw[BW_GTOT];
+        if (otb) otb[n_out] = bo.bw[BW_GTOT];  // (the closing boundary)
+    }
+    s_st[tid] = st;  // (a thread past n_out: btot, above every access)
+    s_p0[tid] = p0;
+    __syncthreads();
+    for (uint32_t i = tid; i < btot; i += kCarryTpb) {
+        uint32_t q = 0;
+#pragma unroll
+        for (uint32_t w = kCarryTpb / 2; w > 0; w >>= 1)
+            if (s_st[q + w] <= i) q += w;
+        const uint32_t a = s_p0[q] + (i - s_st[q]), o = base + i;
+        if (o >= acc_cap) continue;  // (a pool txn longer than the pool's max_txn_acc: nothing past the buffers)
+        if (orecs) orecs[o] = precs[a];
+        if (!okeys) continue;
+        okeys[o] = pkeys[a];
+        otypes[o] = ptypes[a];
+        otxn[o] = blockIdx.x * kCarryTpb + q;
+        if (otables) otables[o] = ptables ? ptables[a] : 0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_bo_fold(const uint32_t *__restrict__ tot, RefillTrack tr,
+                                                    RefillBackoff bo) {
+    if (tot[4]) return;
+    track_fold(tr);
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    unsigned long long v[kTrackSlots], sum = 0;
+#pragma unroll
+    for (uint32_t sl = 0; sl < kTrackSlots; sl++) v[sl] = bo.wpart[sl];
+#pragma unroll
+    for (uint32_t sl = 0; sl < kTrackSlots; sl++) {
+        sum += v[sl];
+        if (v[sl]) bo.wpart[sl] = 0;
+    }
+    if (sum) bo.counters[2] += sum;
+}
+
+void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn, const uint64_t *pkeys,
+                           const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptb, uint32_t pool_n,
+                           uint32_t *cursor, uint32_t n_out, uint64_t acc_cap, uint64_t *okeys, uint8_t *otypes,
+                           uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev, uint32_t *tot, const Counters *ctr,
+                           const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const RefillTrack &trk,
+                           const RefillBackoff &bo) {
+    const uint32_t nb = carry_blocks(n_txn), nbo = carry_blocks(n_out);
+    constexpr uint32_t wpb = kBlock / 64;  // (k_bo_park: a wave per carry block)
+    if (nb) {
+        DV_LAUNCH(k_bo_count, nb, kBlock, 0, s, status, bo.aborts, n_txn, nb, bo.lgD, bo.cls);
+        DV_LAUNCH(k_bo_scan, bo.lgD + 1, kBlock, 0, s, bo.cls, nb, bo.bw + BW_CTOT);
+    }
+    DV_LAUNCH(k_bo_plan, 1, 64, 0, s, nb ? 1 : 0, trk.k, trk.k_next, n_out, cursor, pool_n, ctr, tot, bo);
+    if (nb) DV_LAUNCH(k_bo_park, (nb + wpb - 1) / wpb, kBlock, 0, s, status, n_txn, nb, tot, trk, bo);
+    const uint32_t gs = (bo.cap + kBlock - 1) / kBlock;
+    DV_LAUNCH(k_bo_spill, gs < 1 ? 1 : (gs > 1024 ? 1024 : gs), kBlock, 0, s, tot, bo);
+    DV_LAUNCH(k_bo_gather_count, nbo, kBlock, 0, s, tot, n_out, ptb, pool_n, trk.oids, trk.k_next, bo);
+    DV_LAUNCH(k_bo_scan, 1, kBlock, 0, s, bo.gb, nbo, bo.bw + BW_GTOT);
+    DV_LAUNCH(k_bo_gather_copy, nbo, kBlock, 0, s, tot, n_out, trk.oids, pkeys, ptypes, ptables, ptb, pool_n, precs,
+              okeys, otypes, otxn, otables, orecs, otb, n_acc_dev, acc_cap, bo);
+    if (nb) {
+        const uint32_t gf = (trk.n_bins + 4 + kBlock - 1) / kBlock;
+        DV_LAUNCH(k_bo_fold, gf, kBlock, 0, s, tot, trk, bo);
+    }
 }
 
 // a client batch's per-txn access ranges from its acc_txn (non-decreasing;

@@ -636,6 +636,39 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
                    const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr,
                    const RefillTrack *trk = nullptr);
 
+// The back-off ring's words for one refill (dv_closed_loop_backoff; always
+// with a RefillTrack): behind epoch trk->k (n_txn txns; 0: none, the loop's
+// first refill) its aborted txns are parked in the ring, a txn's a-th abort
+// min(2^(a-1), D) epochs ahead, and epoch trk->k_next is the ring slot that
+// falls due, capped at n_out, then fresh pool txns; every txn's accesses are
+// read from the pool by its identity word's src.  A different launch chain
+// from launch_refill's (nothing is copied from the decided epoch), no-ops
+// under the same skip word tot[4].
+//   aborts / oaborts: the abort counts of the decided epoch and of the one
+//     being built; cls: kBoClasses x carry_blocks(n_txn) per-block class
+//     counts; gb: carry_blocks(n_out) per-block access counts; bw: kBoWords
+//     plan words; wpart: kTrackSlots partial sums of (k - born) at commit,
+//     zero between refills; lost: the context's own count of dropped entries.
+constexpr uint32_t kBoClasses = 5;  // delays 1, 2, 4, 8, 16
+constexpr uint32_t kBoWords = 32;
+struct RefillBackoff {
+    uint32_t D, lgD, cap;
+    uint64_t *park_ids;
+    uint8_t *park_aborts;
+    uint32_t *slot_count;
+    const uint8_t *aborts;
+    uint8_t *oaborts;
+    uint64_t *counters;
+    uint32_t *cls, *gb, *bw;
+    unsigned long long *wpart, *lost;
+};
+void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn, const uint64_t *pkeys,
+                           const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptb, uint32_t pool_n,
+                           uint32_t *cursor, uint32_t n_out, uint64_t acc_cap, uint64_t *okeys, uint8_t *otypes,
+                           uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev, uint32_t *tot, const Counters *ctr,
+                           const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const RefillTrack &trk,
+                           const RefillBackoff &bo);
+
 // ---- Deneva client batches decoded on the device (dvcc_wire.hip)
 // k_wire_check takes kWireWave batches per workgroup (a wave each), the scan
 // kWireChunk batches per chunk, the reply compaction kReplyTile txns per tile.

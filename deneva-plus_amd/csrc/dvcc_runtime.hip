@@ -160,6 +160,19 @@ struct dv_ctx {
         uint32_t next = 0;
     } trk;
     uint32_t *trk_part = nullptr;  // RefillTrack::part (allocated by the first attachment, zero between refills)
+    // dv_closed_loop_backoff: the attached ring (its struct and aborts pointers
+    // copied), and the refill's workspace for bo_nb carry blocks -- the wait
+    // partials and the context's own lost count (8-byte words, first), the plan
+    // words, the class and gather block counts (RefillBackoff); lost_seen: that
+    // count as the last loop call read it
+    struct LoopBo {
+        bool on = false;
+        dv_loop_backoff t{};
+        uint8_t *aborts[2] = {nullptr, nullptr};
+        unsigned long long lost_seen = 0;
+    } bo;
+    uint32_t *bo_ws = nullptr;
+    uint32_t bo_nb = 0;
     uint32_t *gc_tb = nullptr;                       // dv_epoch_group_carry: a batch's ranges (2 x max_txn)
     uint32_t *gc_tot = nullptr;                      // ... 3 totals per batch (kMaxGroupBatches)
     // dv_wire_ingest_device / dv_wire_reply_fields_device (dvcc_wire.hip): the
@@ -714,7 +727,7 @@ void dv_close(dv_ctx *c) {
     void *bufs[] = {c->f0, c->pkey, c->ktag, c->pairs[0], c->pairs[1], c->el, c->ew, c->counts,
                     c->digit_tot, c->rel[0], c->rel[1], c->vb8, c->tlen, c->acc_row,
                     c->ulist[0], c->ulist[1], c->tb_start, c->tb_end, c->desc, c->tile_ctr,
-                    c->abounds, c->tword, c->carry_b, c->carry_tot, c->trk_part,
+                    c->abounds, c->tword, c->carry_b, c->carry_tot, c->trk_part, c->bo_ws,
                     c->status, c->verdict, c->ctr, c->d_acc, c->d_keys, c->d_types,
                     c->d_tables, c->d_commit, c->d_txn, c->d_grant, c->d_tb, c->split_err,
                     c->d_args, c->d_oid, c->tp_dsnap,
@@ -3099,7 +3112,17 @@ LoopForm loop_form(const dv_ctx *c, const dv_epoch_dev *pool, const dv_epoch_dev
 // all fresh), then fresh ones from the pool, in the forms f names
 void enqueue_refill(dv_ctx *c, const dv_epoch_dev *prev, const dv_epoch_dev *prev_buf, const dv_epoch_dev *pool,
                     const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_out, const dv_epoch_dev &out,
-                    LoopForm f = {}, const RefillTrack *trk = nullptr) {
+                    LoopForm f = {}, const RefillTrack *trk = nullptr, const RefillBackoff *bo = nullptr) {
+    if (bo) {  // (the back-off chain: nothing is copied from prev)
+        launch_refill_backoff(c->stream, c->status, prev ? prev->n_txn : 0u, pool->keys, pool->types, pool->tables,
+                              pool_begin, pool->n_txn, cursor, n_out, (uint64_t)n_out * pool->max_txn_acc,
+                              f.old ? const_cast<uint64_t *>(out.keys) : nullptr, const_cast<uint8_t *>(out.types),
+                              const_cast<uint32_t *>(out.acc_txn), const_cast<uint8_t *>(out.tables),
+                              const_cast<uint32_t *>(out.n_acc_dev), c->carry_tot, prev ? c->ctr : nullptr,
+                              f.tb ? pool->recs32 : nullptr, f.tb ? const_cast<uint32_t *>(out.recs32) : nullptr,
+                              f.tb ? const_cast<uint32_t *>(out.txn_begin) : nullptr, *trk, *bo);
+        return;
+    }
     launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u,
                   prev && f.old ? prev->keys : nullptr, prev && f.old ? prev->types : nullptr,
                   prev && f.old ? prev->tables : nullptr, pool->keys, pool->types, pool->tables, pool->acc_txn,
@@ -3135,6 +3158,44 @@ const RefillTrack *track_at(const dv_ctx *t, bool prev, uint32_t k, uint32_t k_n
     w->part = t->trk_part;
     return w;
 }
+// The back-off ring (dv_closed_loop_backoff) of context t for the same refill
+// (ib / ob: the decided and the built epoch's buffers).  NULL when nothing is
+// attached.
+const RefillBackoff *backoff_at(const dv_ctx *t, uint32_t ib, uint32_t ob, RefillBackoff *w) {
+    if (!t->bo.on) return nullptr;
+    const dv_loop_backoff &d = t->bo.t;
+    w->D = d.n_slots;
+    w->lgD = (uint32_t)bits_for(d.n_slots);
+    w->cap = d.slot_cap;
+    w->park_ids = d.park_ids;
+    w->park_aborts = d.park_aborts;
+    w->slot_count = d.slot_count;
+    w->aborts = t->bo.aborts[ib];
+    w->oaborts = t->bo.aborts[ob];
+    w->counters = d.counters;
+    unsigned long long *w64 = reinterpret_cast<unsigned long long *>(t->bo_ws);
+    w->wpart = w64;
+    w->lost = w64 + kTrackSlots;
+    w->bw = t->bo_ws + 2 * (kTrackSlots + 1);
+    w->cls = w->bw + kBoWords;
+    w->gb = w->cls + (size_t)kBoClasses * t->bo_nb;
+    return w;
+}
+// the back-off workspace for nb carry blocks (zeroed when allocated)
+int backoff_bufs(dv_ctx *c, uint32_t nb) {
+    if (!c->bo.on || (c->bo_ws && nb <= c->bo_nb)) return DV_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dfree(c->bo_ws);
+    c->bo_ws = nullptr;
+    c->bo_nb = 0;
+    const uint64_t words = 2ull * (kTrackSlots + 1) + kBoWords + (uint64_t)(kBoClasses + 1) * nb;
+    int r = dalloc(&c->bo_ws, words);
+    if (r) return r;
+    HIPCHK(hipMemset(c->bo_ws, 0, sizeof(uint32_t) * words));
+    c->bo_nb = nb;
+    c->bo.lost_seen = 0;
+    return DV_OK;
+}
 // a loop call over n_bufs buffers and n_epochs epochs against the attachment
 int track_check(const dv_ctx *t, uint32_t n_bufs, uint32_t n_epochs) {
     if (!t->trk.on) return DV_OK;
@@ -3165,9 +3226,11 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     int r = carry_bufs(c, carry_blocks(n_txn));
+    if (!r) r = backoff_bufs(c, carry_blocks(n_txn));
     if (r) return r;
     const LoopForm form = loop_form(c, pool, bufs, 2, n_txn);
     RefillTrack tw;
+    RefillBackoff bw;
     // epoch k's descriptor: buffer k & 1, its access count on the device
     auto desc = [&](uint32_t k) {
         dv_epoch_dev d = bufs[k & 1];
@@ -3188,7 +3251,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     };
     if (!resume)
         enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, bufs[0], form,
-                       track_at(c, false, 0, 0, 0, 0, 1, &tw));
+                       track_at(c, false, 0, 0, 0, 0, 1, &tw), backoff_at(c, 0, 0, &bw));
     const dv_epoch_dev d0 = desc(0);
     const bool pipelined = prefix_applies(c, &d0) && !timing(c) && !ktiming(c) && !c->rep_P;
     EpochSnap snap[2];
@@ -3199,7 +3262,8 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, stats_of(k));
         if (!e) {
             enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
-                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw));
+                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
+                           backoff_at(c, k & 1, (k + 1) & 1, &bw));
             e = hip_fail(hipGetLastError(), "refill");
         }
         return e;
@@ -3217,7 +3281,8 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
             // behind the execution: epoch k + 1 from epoch k's final statuses (a
             // no-op when k halted -- the host redoes both below)
             enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
-                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw));
+                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
+                           backoff_at(c, k & 1, (k + 1) & 1, &bw));
             r = hip_fail(hipGetLastError(), "refill");
         }
         if (r) {
@@ -3259,6 +3324,14 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
     c->trk.next += c->trk.on ? n_epochs : 0u;
+    if (c->bo.on) {  // capacity exceeded in this call: entries were dropped (counted, dv_loop_backoff::counters[1])
+        unsigned long long lost = 0;
+        HIPCHK(hipMemcpy(&lost, reinterpret_cast<unsigned long long *>(c->bo_ws) + kTrackSlots, sizeof(lost),
+                         hipMemcpyDeviceToHost));
+        const bool more = lost != c->bo.lost_seen;
+        c->bo.lost_seen = lost;
+        if (more) return DV_ERR_ARG;
+    }
     return DV_OK;
 }
 
@@ -3278,7 +3351,7 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
         c->cfg.workload != DV_TPCC)
         return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
-    if (c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
+    if (c->cfg.cc_alg == DV_CALVIN || c->comm || c->bo.on) return DV_ERR_STATE;  // (bo: the single YCSB loop only)
     const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
     if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
         bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn || !pool->tables)
@@ -3354,6 +3427,8 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     if (!pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
     dv_ctx *const c0 = lanes[0];
     if (c0->cfg.cc_alg == DV_CALVIN || c0->cfg.workload != DV_YCSB) return DV_ERR_STATE;
+    for (uint32_t l = 0; l < n_lanes; l++)
+        if (lanes[l]->bo.on) return DV_ERR_STATE;  // (a ring per lane: not built)
     const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
     if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c0->cfg.max_txn || bound > buf_cap ||
         bound > c0->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn)
@@ -3435,6 +3510,7 @@ int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
     if (!c) return DV_ERR_ARG;
     if (!trk) {
         c->trk = dv_ctx::LoopTrk{};
+        c->bo.on = false;  // (the back-off rides on the tracker)
         return DV_OK;
     }
     if (!trk->ids || !trk->n_bufs || (trk->n_bufs & 1) || trk->n_bufs > 2 * kMaxLanes || !trk->log ||
@@ -3455,6 +3531,27 @@ int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
     c->trk.ids.assign(trk->ids, trk->ids + trk->n_bufs);
     c->trk.t.ids = nullptr;  // (the caller's array is not kept: ids above)
     c->trk.next = trk->first_epoch;
+    return DV_OK;
+}
+
+int dv_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) {
+    if (!c) return DV_ERR_ARG;
+    if (!bo) {
+        c->bo.on = false;
+        return DV_OK;
+    }
+    const uint32_t D = bo->n_slots;
+    if ((D != 1 && D != 2 && D != 4 && D != 8 && D != 16) || !bo->slot_cap || !bo->park_ids || !bo->park_aborts ||
+        !bo->slot_count || !bo->aborts || !bo->aborts[0] || !bo->aborts[1] || !bo->counters ||
+        (uint64_t)D * bo->slot_cap > 0xFFFFFFFFull)
+        return DV_ERR_ARG;
+    if (c->phase != 0 || c->cfg.cc_alg == DV_CALVIN || c->comm || !c->trk.on || c->trk.t.n_bufs != 2)
+        return DV_ERR_STATE;
+    c->bo.on = true;
+    c->bo.t = *bo;
+    c->bo.aborts[0] = bo->aborts[0];
+    c->bo.aborts[1] = bo->aborts[1];
+    c->bo.t.aborts = nullptr;  // (the caller's array is not kept)
     return DV_OK;
 }
 

@@ -168,6 +168,12 @@ class LoopTrackDesc(ctypes.Structure):  # dv_loop_track (dv_closed_loop_track; d
                 ("retry_hist", ctypes.c_void_p), ("n_bins", ctypes.c_uint32), ("totals", ctypes.c_void_p)]
 
 
+class LoopBackoffDesc(ctypes.Structure):  # dv_loop_backoff (dv_closed_loop_backoff; dvcc.LoopBackoff owns the arrays)
+    _fields_ = [("n_slots", ctypes.c_uint32), ("slot_cap", ctypes.c_uint32), ("park_ids", ctypes.c_void_p),
+                ("park_aborts", ctypes.c_void_p), ("slot_count", ctypes.c_void_p),
+                ("aborts", ctypes.POINTER(ctypes.c_void_p)), ("counters", ctypes.c_void_p)]
+
+
 # TPC-C table ids and operation words (include/dvcc.h)
 T_WAREHOUSE, T_DISTRICT, T_CUSTOMER, T_ITEM, T_STOCK, T_CUST_LAST = 0, 1, 2, 3, 4, 5
 TOP_NONE, TOP_PAY_WH, TOP_PAY_DIST, TOP_PAY_CUST, TOP_NO_DIST, TOP_NO_STOCK = 0, 1, 2, 3, 4, 5
@@ -273,6 +279,7 @@ SIGNATURES = [
                                                    _P(ctypes.c_uint32)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
     ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
+    ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
 ]
 
 _lib = None

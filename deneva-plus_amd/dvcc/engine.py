@@ -299,6 +299,9 @@ class LoopTrack:
     def detach(self):
         if self.engine is not None:
             L.check(L.lib().dv_closed_loop_track(self.engine._ctx, None), "dv_closed_loop_track")
+            bo = getattr(self.engine, "_backoff", None)
+            if bo is not None:  # (the back-off rides on the tracker: detached with it)
+                bo.engine, self.engine._backoff = None, None
             self.engine._track = None
             self.engine = None
 
@@ -345,6 +348,78 @@ class LoopTrack:
     def overflowed(self):
         """commits counted past log_cap (not written)"""
         return max(0, (int(self.log_pos.item()) & 0xFFFFFFFF) - self.log_cap)
+
+
+class LoopBackoff:
+    """Exponential back-off for the single YCSB closed loop
+    (dv_closed_loop_backoff): a ring of n_slots slots of slot_cap parked txns
+    (identity word and abort count), the two epoch buffers' abort counts and
+    the four counters -- device tensors this object owns.  Built over a
+    LoopTrack of two buffers; attach() it after the tracker, to the same
+    engine, and call swap() beside ClosedLoopBufs.swap and LoopTrack.swap.
+    slot_cap defaults to the bound n_txn * (D + log2 D), which no run
+    exceeds; detaching the tracker detaches the back-off."""
+
+    def __init__(self, track, n_slots, slot_cap=None, device="cuda"):
+        import torch
+        if track.n_bufs != 2:
+            raise ValueError("LoopBackoff: a single loop's two buffers only")
+        self.track, self.n_slots, self.n_txn = track, int(n_slots), track.n_txn
+        lg = max(0, self.n_slots.bit_length() - 1)
+        self.slot_cap = int(slot_cap) if slot_cap is not None else self.n_txn * (self.n_slots + lg)
+        z = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=device)  # noqa: E731
+        n = max(1, self.n_slots) * self.slot_cap
+        self.park_ids, self.park_aborts = z(n, torch.int64), z(n, torch.uint8)
+        self.slot_count = z(max(1, self.n_slots), torch.int32)
+        self.aborts = [z(self.n_txn, torch.uint8) for _ in range(2)]
+        self.ctr = z(4, torch.int64)
+        self.engine = None
+
+    def _attach(self):
+        arr = (ctypes.c_void_p * 2)(*[int(t.data_ptr()) for t in self.aborts])
+        d = L.LoopBackoffDesc(self.n_slots, self.slot_cap, self.park_ids.data_ptr(), self.park_aborts.data_ptr(),
+                              self.slot_count.data_ptr(), arr, self.ctr.data_ptr())
+        L.check(L.lib().dv_closed_loop_backoff(self.engine._ctx, ctypes.byref(d)), "dv_closed_loop_backoff")
+
+    def attach(self, engine):
+        """Backs off `engine`'s closed loop (its tracker attached first).  The
+        tensors stay as they are: a ring left by earlier calls is continued."""
+        self.engine = engine
+        try:
+            self._attach()
+        except Exception:
+            self.engine = None
+            raise
+        engine._backoff = self
+        return self
+
+    def detach(self):
+        if self.engine is not None:
+            L.check(L.lib().dv_closed_loop_backoff(self.engine._ctx, None), "dv_closed_loop_backoff")
+            self.engine._backoff = None
+            self.engine = None
+
+    def swap(self):
+        """with ClosedLoopBufs.swap and LoopTrack.swap (call it after the
+        tracker's), after a call of n_epochs odd: the next epoch's abort
+        counts move to buffer 0 too"""
+        self.aborts.reverse()
+        if self.engine is not None:
+            self._attach()
+
+    def counters(self):
+        """spilled, lost, the sum over commits of (k - born), txns parked now"""
+        return [int(v) for v in self.ctr.cpu().numpy()]
+
+    def parked(self):
+        """the slots' contents: per slot (src, born, aborts) as numpy arrays"""
+        cnt = self.slot_count.cpu().numpy().view(np.uint32)
+        ids, ab = self.park_ids.cpu().numpy(), self.park_aborts.cpu().numpy()
+        out = []
+        for s in range(self.n_slots):
+            lo, hi = s * self.slot_cap, s * self.slot_cap + min(int(cnt[s]), self.slot_cap)
+            out.append((ids[lo:hi] & 0xFFFFFFFF, ids[lo:hi] >> 32, ab[lo:hi].copy()))
+        return out
 
 
 def _loop_tb(pool, bufs):
@@ -428,7 +503,7 @@ class CCEngine:
         configuration over this engine's tables (loaded first; frozen while
         lanes are open).  Closed with, or before, this engine."""
         lane = type(self).__new__(type(self))
-        own = ("_ctx", "_lanes", "_ev", "_ext", "_track")
+        own = ("_ctx", "_lanes", "_ev", "_ext", "_track", "_backoff")
         lane.__dict__.update({k: v for k, v in self.__dict__.items() if k not in own})
         lane._ctx = ctypes.c_void_p()
         L.check(L.lib().dv_open_lane(self._ctx, ctypes.byref(lane._ctx)), "dv_open_lane")

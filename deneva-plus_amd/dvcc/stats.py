@@ -74,7 +74,8 @@ def summary_line(total_runtime_s, stats, prog=False, **kw):
     return ("[prog] " if prog else "[summary] ") + body
 
 
-def retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, epoch_seconds=None, **kw):
+def retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, epoch_seconds=None,
+                         wait_epochs=None, **kw):
     """summary_fields for a closed loop run under a loop tracker: the same keys,
     with what the tracker knows about retries.  totals / hist: LoopTrack.totals()
     (committed, aborted, first aborts, max retries) and LoopTrack.histogram()
@@ -87,7 +88,11 @@ def retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, e
     epochs of the mean epoch time (epoch_seconds' mean when given, else the
     run's share), from the histogram -- exact while no commit lands in its last,
     saturating bin (every commit there is charged n_bins - 1 retries: a lower
-    bound); txn_run_avg_time divides by the commits."""
+    bound); txn_run_avg_time divides by the commits.
+    wait_epochs (a loop under back-off, LoopBackoff.counters()[2]: the sum over
+    the commits of k - born): txn_run_time charges wait_epochs + commits epochs
+    instead -- exact, whatever delays the retries took and with no saturating
+    bin; penalty_epochs is then not used."""
     base = dict(summary_fields(total_runtime_s, stats, epoch_seconds=epoch_seconds, **kw))
     hist = [int(h) for h in hist]
     n_ep = len(stats)
@@ -95,8 +100,11 @@ def retry_summary_fields(total_runtime_s, stats, totals, hist, penalty_epochs, e
         per = sum(float(e) for e in epoch_seconds) / len(epoch_seconds)
     else:
         per = float(total_runtime_s) / n_ep if n_ep else 0.0
-    run_time = sum(h * (r * int(penalty_epochs) + 1) for r, h in enumerate(hist)) * per
     commits = sum(hist)
+    if wait_epochs is not None:
+        run_time = (int(wait_epochs) + commits) * per
+    else:
+        run_time = sum(h * (r * int(penalty_epochs) + 1) for r, h in enumerate(hist)) * per
     base["unique_txn_abort_cnt"] = int(totals[2])
     base["txn_run_time"] = run_time
     base["txn_run_avg_time"] = run_time / commits if commits else 0.0

@@ -582,6 +582,75 @@ typedef struct dv_loop_track {
 } dv_loop_track;
 int dv_closed_loop_track(dv_ctx *ctx, const dv_loop_track *trk);
 
+/* Exponential back-off for retried txns: an optional attachment to the
+ * single-context YCSB closed loop (dv_epoch_run_closed_loop), on top of its
+ * tracker.  The reference's AbortQueue::enqueue (abort_queue.cpp:26-31) meant
+ * penalty * 2^abort_cnt capped at a maximum; it is written with ^ as XOR and
+ * max in place of min, so it does not back off.  Here the
+ * penalty is counted in epochs and kept entirely on the device: a txn's a-th
+ * abort costs min(2^(a-1), D) epochs, D = n_slots the longest delay.
+ *   State: a ring of D slots, each an ordered list of parked txns -- a txn's
+ *     identity word (the tracker's src | born << 32, unchanged) and its abort
+ *     count, a byte that saturates at 255 (0 for a fresh txn): 9 bytes a txn.
+ *     Loop epochs are numbered as the tracker numbers them.
+ *   After epoch k is decided, park: each aborted txn, in sequence order, with
+ *     a = its aborts + 1, is appended to slot (k + min(2^(a-1), D)) % D.  The
+ *     delays 1, 2, 4, ..., D fall into distinct slots; each appends to its own
+ *     in sequence order.
+ *   Then build epoch k + 1: slot s = (k + 1) % D holds c entries; the first
+ *     R = min(c, n_txn), in slot order, open the epoch; the other c - R (the
+ *     spill) are appended, in order, to the tail of slot (k + 2) % D as it
+ *     then stands, and slot s is empty.  F = n_txn - R fresh txns follow from
+ *     the pool at the cursor, as in the plain loop.  A released txn's accesses
+ *     are read from the pool again by its src (the query is unchanged, as
+ *     dv_epoch_carry keeps it).
+ *   The first epoch of a call without resume is built by the same release
+ *     with no park before it: an empty ring gives an all-fresh epoch.
+ *   D = 1 is the plain loop (every delay 1, nothing spills), bit for bit:
+ *     epochs, commit bytes, cursor, log, histogram, totals.
+ *   Capacity: a slot never holds more than n_txn * (D + log2 D) entries
+ *     (the spill of a slot is at most n_txn * (D - 1): aborts of epoch k fall
+ *     due in k + 1 .. k + D).  With a smaller slot_cap, entries at positions
+ *     >= slot_cap are counted in counters[1] and not written -- nothing is
+ *     stored past any array -- and the loop call in which that happened
+ *     returns DV_ERR_ARG (capacity exceeded) after its last epoch: one 8-byte
+ *     read per call, none between epochs.
+ *   With a back-off attached the tracker's histogram bins a commit by its
+ *     abort count, totals[3] is the largest abort count at a commit, and a
+ *     first abort is an abort with incoming count 0; the log and epoch_end are
+ *     unchanged.  At D = 1 all of this is what the tracker records alone.
+ *   counters[4], added to: entries spilled, entries lost, the sum over commits
+ *     of (k - born) -- the epochs from a txn's first run to its commit -- and
+ *     [3], stored, not added: the txns parked after the last refill.
+ * Attaching touches no device memory (the caller zeroes slot_count and the
+ * counters for a new loop, and the aborts arrays with the tracker's ids); the
+ * struct and the two aborts pointers are copied.  A caller that swaps the
+ * loop's buffers after an odd n_epochs attaches again with aborts swapped too
+ * (dvcc.LoopBackoff.swap).  Requires a tracker with n_bufs == 2 attached to
+ * the context; detaching the tracker detaches the back-off.  NULL detaches.
+ * Refused at attach time: a null context, array or aborts entry, n_slots not
+ * 1, 2, 4, 8 or 16, slot_cap 0, a ring of 2^32 entries or more
+ * (DV_ERR_ARG); no tracker, one of more than two buffers, a CALVIN context or
+ * one with a communicator (DV_ERR_STATE).  With a back-off attached
+ * dv_epoch_run_closed_loop_lanes (n_lanes > 1) and dv_tpcc_epoch_run_closed_loop
+ * return DV_ERR_STATE before any launch.
+ * The refill is then a different chain (k_bo_count, k_bo_scan, k_bo_plan,
+ * k_bo_park, k_bo_spill, k_bo_gather_count, k_bo_scan, k_bo_gather_copy,
+ * k_bo_fold: dvcc_carry.hip), a no-op behind a halted or failed epoch like the
+ * plain one, outside any captured epoch graph.  Without a back-off the loops
+ * launch exactly what they launched before. */
+typedef struct dv_loop_backoff {
+    uint32_t n_slots;         /* D: 1, 2, 4, 8 or 16 = the longest delay in epochs          */
+    uint32_t slot_cap;        /* entries per slot                                            */
+    uint64_t *park_ids;       /* device [n_slots * slot_cap] identity words                  */
+    uint8_t  *park_aborts;    /* device [n_slots * slot_cap]                                 */
+    uint32_t *slot_count;     /* device [n_slots], in/out: the caller zeroes it for a new loop */
+    uint8_t *const *aborts;   /* [2] device arrays, n_txn bytes: the abort counts of bufs[i] */
+    uint64_t *counters;       /* device [4], added to: spilled, lost, sum over commits of
+                                 (k - born), txns parked now (a level, stored not added)     */
+} dv_loop_backoff;
+int dv_closed_loop_backoff(dv_ctx *ctx, const dv_loop_backoff *bo);   /* NULL detaches */
+
 /* Epoch groups -- epoch-parallel scheduling for YCSB: a
  * group is P = nranks consecutive epochs of the sequencer, and homes[e]
  * (n_homes == P) is this rank's client batch of epoch e (txn ids local,
