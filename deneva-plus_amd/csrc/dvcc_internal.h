@@ -330,12 +330,13 @@ void launch_probe_tb(hipStream_t s, const Tables &tabs, const uint64_t *keys, co
 
 // stable LSD radix sort of pairs on bits [32, 32 + key_bits); returns the index
 // (0/1) of the buffer holding the result.  counts: >= kRadix * nblocks(n),
-// digit_tot: kRadix.  scatter_ev (optional): 2 events per pass for timing.
+// digit_tot: 2 * kRadixMax (the digits' totals, then the exclusive prefix of
+// them that a bucket sort's workgroups start from).  scatter_ev (optional): 2 events per pass for timing.
 // n_dev (optional): the real count on the device, n an upper bound.
 // digit width of radix_sort_rows: 8 bits, or 9-10 when that saves a pass
 // (never when the probe counted the first 8-bit histogram)
 constexpr int kRadixMaxBits = 10;
-constexpr int kRadixMax = 1 << kRadixMaxBits;  // counts: kRadixMax x sort tiles, digit_tot: kRadixMax
+constexpr int kRadixMax = 1 << kRadixMaxBits;  // counts: kRadixMax x sort tiles, digit_tot: 2 x kRadixMax
 inline int radix_digit_bits(int key_bits, bool hist0_done) {
     const int p8 = (key_bits + kRadixBits - 1) / kRadixBits;
     if (hist0_done || p8 < 2) return kRadixBits;

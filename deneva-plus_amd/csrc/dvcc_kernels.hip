@@ -530,7 +530,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_scan(uint32_t *__restrict__ co
 __global__ __launch_bounds__(kBlock) void k_radix_scatter(
     const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n, int shift, const uint32_t *__restrict__ counts,
     const uint32_t *__restrict__ digit_tot, uint32_t nblocks, const uint32_t *__restrict__ n_dev,
-    uint32_t hmul, int hbits) {
+    uint32_t hmul, int hbits, uint32_t *__restrict__ digit_pre) {
     __shared__ __attribute__((aligned(16))) uint64_t skeys[kTile];
     n = sort_n(n, n_dev);
     if ((uint64_t)blockIdx.x * kTile >= n) return;
@@ -546,6 +546,8 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter(
     {
         const uint32_t d = tid;  // kBlock == kRadix
         const uint32_t dex = block_excl_scan256(digit_tot[d], lds4, nullptr);
+        // (a bucket sort's pass: the first tile leaves the buckets' offsets to k_bucket_sort)
+        if (digit_pre && blockIdx.x == 0) digit_pre[d] = dex;
         gbase[d] = (uint64_t)dex + counts[(uint64_t)d * nblocks + blockIdx.x];
         for (int w = 0; w < 4; w++) wc[w][d] = 0;
     }
@@ -650,7 +652,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter_w(const uint64_t *__re
                                                             uint64_t n, int shift, const uint32_t *__restrict__ counts,
                                                             const uint32_t *__restrict__ digit_tot, uint32_t nblocks,
                                                             const uint32_t *__restrict__ n_dev, uint32_t hmul,
-                                                            int hbits) {
+                                                            int hbits, uint32_t *__restrict__ digit_pre) {
     constexpr uint32_t R = 1u << W, PER = R / kBlock;  // digits per thread in the digit scans
     __shared__ __attribute__((aligned(16))) uint64_t skeys[kTile];
     __shared__ uint32_t wc[4][R];
@@ -674,6 +676,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter_w(const uint64_t *__re
 #pragma unroll
         for (uint32_t q = 0; q < PER; q++) {
             const uint32_t d = tid * PER + q;
+            if (digit_pre && blockIdx.x == 0) digit_pre[d] = pre;
             gbase[d] = pre + counts[(uint64_t)d * nblocks + blockIdx.x];
             pre += t[q];
             wc[0][d] = wc[1][d] = wc[2][d] = wc[3][d] = 0;
@@ -748,11 +751,11 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter_w(const uint64_t *__re
 template <int W>
 void wide_pass(hipStream_t s, const uint64_t *in, uint64_t *out, uint64_t n, int shift, uint32_t *counts,
                uint32_t *digit_tot, uint32_t nb, const uint32_t *n_dev, hipEvent_t e0, hipEvent_t e1,
-               uint32_t hmul = 0, int hbits = 0) {
+               uint32_t hmul = 0, int hbits = 0, uint32_t *digit_pre = nullptr) {
     DV_LAUNCH((k_radix_hist_w<W>), nb, kBlock, 0, s, in, n, shift, counts, nb, n_dev, hmul, hbits);
     DV_LAUNCH(k_radix_scan, 1u << W, kBlock, 0, s, counts, nb, digit_tot, n_dev);
     DV_LAUNCH_EV((k_radix_scatter_w<W>), nb, kBlock, 0, s, e0, e1, in, out, n, shift,
-                          (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, hmul, hbits);
+                          (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, hmul, hbits, digit_pre);
 }
 
 // ---- bucket sort (small sorts, dvcc_internal.h bucket_sort_applies) --------
@@ -763,21 +766,50 @@ void wide_pass(hipStream_t s, const uint64_t *in, uint64_t *out, uint64_t n, int
 // bucket) in LDS with 8-bit digits, wave-ballot ranks as in k_radix_scatter,
 // and finally gathers the keys (L2-resident: the bucket was just read) into
 // place.  A bucket larger than its LDS (a hot row read by many survivors)
-// is sorted the same way from global memory, in 16K-key chunks, with the
-// bucket's region of the input buffer as the ping-pong scratch.
-constexpr int kBucketThreads = 1024;
+// is sorted the same way from global memory, in chunks of kBucketGroup steps,
+// with the bucket's region of the input buffer as the ping-pong scratch.
+// The tags are sorted in place: a pass reads all of a thread's tags and ranks
+// them before the barrier and scatters them into the same array after it, so
+// a 512-thread workgroup holds 74 KiB of LDS and two of them share a CU
+// (under the decision lanes' 64-CU masks a launch's 256 buckets take two
+// rounds of workgroups instead of four).
+#ifndef DVCC_BUCKET_THREADS
+#define DVCC_BUCKET_THREADS 512  // (256 / 512 / 1024: DESIGN.md section 4, small sorts)
+#endif
+constexpr int kBucketThreads = DVCC_BUCKET_THREADS;
+static_assert(kBucketThreads == 256 || kBucketThreads == 512 || kBucketThreads == 1024, "DVCC_BUCKET_THREADS");
 constexpr int kBucketWaves = kBucketThreads / 64;
 constexpr int kBucketIdxBits = 32 - kBucketHiMax;
 constexpr uint32_t kBucketCap = 1u << kBucketIdxBits;       // keys a workgroup sorts in LDS
 constexpr int kBucketSteps = (int)kBucketCap / kBucketThreads;  // 64-key steps per wave, at most
-// two tag arrays + per-wave digit counts: one workgroup per CU on gfx950
-static_assert((2 * kBucketCap + (kBucketWaves + 2) * kRadix + kBucketWaves) * sizeof(uint32_t) <= 160u * 1024u,
-              "k_bucket_sort's LDS exceeds gfx950's 160 KiB per workgroup");
+constexpr int kBucketGroup = 16;  // steps whose 8-byte keys a thread holds at once (loads in flight together)
+static_assert(kBucketSteps % kBucketGroup == 0, "k_bucket_sort walks its keys in whole groups of steps");
+// one tag array + per-wave digit counts + tot, run: workgroups of at most 512
+// threads fit twice into gfx950's 160 KiB (and into its 32 waves) per CU
+constexpr uint32_t kBucketLds = (kBucketCap + (kBucketWaves + 2) * kRadix) * sizeof(uint32_t);
+constexpr int kBucketPerCu = kBucketThreads <= 512 ? 2 : 1;
+static_assert(kBucketPerCu * kBucketLds <= 160u * 1024u, "k_bucket_sort's workgroups exceed gfx950's 160 KiB of LDS per CU");
+constexpr int kBucketWavesPerSimd = kBucketPerCu * kBucketWaves / 4;  // (the register budget that goes with it)
+
+// match_digit with the lane's own bit spread to a word, g = 0 or ~0, so that
+// "the lanes whose bit equals mine" is ~(ballot ^ g): six vector instructions
+// a bit; the select form compiles to eleven
+__device__ __forceinline__ uint64_t bucket_match(uint32_t d, uint64_t valid) {
+    uint32_t lo = (uint32_t)valid, hi = (uint32_t)(valid >> 32);
+#pragma unroll
+    for (int b = 0; b < kRadixBits; b++) {
+        const uint32_t g = (uint32_t)((int32_t)(d << (31 - b)) >> 31);
+        const uint64_t m = __ballot((d & (1u << b)) != 0u);
+        lo &= ~((uint32_t)m ^ g);
+        hi &= ~((uint32_t)(m >> 32) ^ g);
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
 
 // stable rank of this lane's digit among the wave's keys so far (wcw: the
 // wave's running digit counts, updated)
 __device__ __forceinline__ uint32_t bucket_rank(uint32_t d, bool valid, uint32_t *wcw, uint32_t lane) {
-    const uint64_t peers = match_digit(d, __ballot(valid));
+    const uint64_t peers = bucket_match(d, __ballot(valid));
     const uint32_t before = wcw[d];
     if (valid && lane == (uint32_t)__builtin_ctzll(peers)) wcw[d] = before + (uint32_t)__popcll(peers);
     return before + mask_rank(peers);
@@ -786,40 +818,42 @@ __device__ __forceinline__ uint32_t bucket_rank(uint32_t d, bool valid, uint32_t
 // wc[w][d] (keys of digit d in wave w's part of the chunk) -> the position of
 // that part's first key: run[d] (the digit's next free slot; advanced by the
 // digit's chunk total) or, with run == nullptr, the chunk's own digit-major
-// offsets.  Called by every thread.
+// offsets.  Called by every thread.  A digit's thread loads all its waves'
+// counts at once and prefixes them in registers (no chain of LDS round trips);
+// the 256 digit totals are scanned where they are, by a wave scan in each of
+// the four waves that hold them plus those waves' totals (tot[0..4)).
 __device__ __forceinline__ void bucket_bases(uint32_t (*wc)[kRadix], uint32_t *tot, uint32_t *run) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63;
-    uint32_t sum = 0;
-    if (tid < (uint32_t)kRadix) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool mine = tid < (uint32_t)kRadix;
+    uint32_t c[kBucketWaves], sum = 0, b = 0;
+    if (mine) {
+#pragma unroll
+        for (int w = 0; w < kBucketWaves; w++) c[w] = wc[w][tid];
 #pragma unroll
         for (int w = 0; w < kBucketWaves; w++) {
-            const uint32_t c = wc[w][tid];
-            wc[w][tid] = sum;
-            sum += c;
+            const uint32_t v = c[w];
+            c[w] = sum;
+            sum += v;
         }
-        if (!run) tot[tid] = sum;
-    }
-    __syncthreads();
-    if (!run && tid < 64) {  // exclusive scan of the 256 digit totals, 4 per lane
-        uint32_t v[4], s4 = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            v[q] = tot[4 * lane + q];
-            s4 += v[q];
-        }
-        uint32_t pre = wave_incl_sum(s4, lane) - s4;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            tot[4 * lane + q] = pre;
-            pre += v[q];
+        if (run) {
+            b = run[tid];
+            run[tid] = b + sum;
+        } else {
+            b = wave_incl_sum(sum, lane);
+            if (lane == 63) tot[wave] = b;
+            b -= sum;
         }
     }
-    if (!run) __syncthreads();
-    if (tid < (uint32_t)kRadix) {
-        const uint32_t b = run ? run[tid] : tot[tid];
-        if (run) run[tid] = b + sum;
+    if (!run) {
+        __syncthreads();
+        if (mine) {
 #pragma unroll
-        for (int w = 0; w < kBucketWaves; w++) wc[w][tid] += b;
+            for (uint32_t w = 0; w < (uint32_t)kRadix / 64 - 1; w++) b += w < wave ? tot[w] : 0u;
+        }
+    }
+    if (mine) {
+#pragma unroll
+        for (int w = 0; w < kBucketWaves; w++) wc[w][tid] = c[w] + b;
     }
     __syncthreads();
 }
@@ -829,73 +863,88 @@ __device__ __forceinline__ void bucket_bases(uint32_t (*wc)[kRadix], uint32_t *t
 // bucket, summed over launches -- [0] launches, [1] wall-clock ticks (100 MHz)
 // from the workgroup's start to its end, [2] keys, [3] the most ticks of one
 // launch; g_bucket_launch: [0] launches, [1] sum of the launch's slowest
-// bucket's ticks, [2] that bucket's keys, [3] the last-workgroup ticket
+// bucket's ticks, [2] that bucket's keys, [3] unused.  Launches of several
+// contexts (decision lanes) overlap, so what belongs to one launch -- the
+// last-workgroup ticket, the slowest bucket, the first workgroup's start and
+// the last one's end -- is kept per context, in the slot its digit_tot
+// pointer claims: g_bucket_ctx[slot] = [0] launches, [1] sum of the launches'
+// spans (first start to last end, ticks), [2] the longest span, [3] ticket,
+// [4] the running launch's slowest bucket, [5] its earliest start, [6] its
+// latest end, [7] the slot's key
+constexpr int kStampSlots = 8;
 __device__ unsigned long long g_bucket_stamps[1024 * 4];
 __device__ unsigned long long g_bucket_launch[4];
-__device__ unsigned long long g_bucket_lmax;
+__device__ unsigned long long g_bucket_ctx[kStampSlots * 8];
 struct BucketStamp {
     uint64_t t0;
     __device__ BucketStamp() : t0(wall_clock64()) {}
-    __device__ void done(uint32_t b, uint32_t m) {
+    __device__ void done(uint32_t b, uint32_t m, const void *ctx_key) {
         __syncthreads();
         if (threadIdx.x != 0) return;
-        const unsigned long long dt = wall_clock64() - t0;
+        const unsigned long long t1 = wall_clock64(), dt = t1 - t0;
         unsigned long long *w = g_bucket_stamps + (size_t)b * 4;
         atomicAdd(w + 0, 1ull);
         atomicAdd(w + 1, dt);
         atomicAdd(w + 2, (unsigned long long)m);
         atomicMax(w + 3, dt);
-        atomicMax(&g_bucket_lmax, (dt << 20) | m);
+        unsigned long long *c = nullptr;
+        for (int i = 0; i < kStampSlots && !c; i++) {
+            const unsigned long long k = atomicCAS(&g_bucket_ctx[i * 8 + 7], 0ull, (unsigned long long)ctx_key);
+            if (k == 0ull || k == (unsigned long long)ctx_key) c = g_bucket_ctx + i * 8;
+        }
+        if (!c) return;  // (more contexts than slots: not counted)
+        atomicMax(c + 4, (dt << 20) | m);
+        atomicMax(c + 5, ~t0);  // (~start, so that 0 is "none yet")
+        atomicMax(c + 6, t1);
         __threadfence();
-        if (atomicAdd(&g_bucket_launch[3], 1ull) == (unsigned long long)gridDim.x - 1) {
+        if (atomicAdd(c + 3, 1ull) == (unsigned long long)gridDim.x - 1) {
             __threadfence();
-            const unsigned long long mx = atomicExch(&g_bucket_lmax, 0ull);
+            const unsigned long long mx = atomicExch(c + 4, 0ull);
+            const unsigned long long first = ~atomicExch(c + 5, 0ull), last = atomicExch(c + 6, 0ull);
             atomicAdd(&g_bucket_launch[0], 1ull);
             atomicAdd(&g_bucket_launch[1], mx >> 20);
             atomicAdd(&g_bucket_launch[2], mx & 0xFFFFFull);
-            g_bucket_launch[3] = 0;
+            c[0] += 1;
+            c[1] += last - first;
+            if (last - first > c[2]) c[2] = last - first;
+            c[3] = 0;
         }
     }
 };
+// out: 1024 x 4 words (g_bucket_stamps), launch: 4 + kStampSlots x 8 words
 extern "C" int dv_debug_bucket_stamps(uint64_t *out, uint64_t *launch) {
     if (!out || !launch) return DV_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return DV_ERR_HIP;
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bucket_stamps), 1024 * 4 * 8) != hipSuccess) return DV_ERR_HIP;
     if (hipMemcpyFromSymbol(launch, HIP_SYMBOL(g_bucket_launch), 4 * 8) != hipSuccess) return DV_ERR_HIP;
+    if (hipMemcpyFromSymbol(launch + 4, HIP_SYMBOL(g_bucket_ctx), kStampSlots * 8 * 8) != hipSuccess) return DV_ERR_HIP;
     static const unsigned long long zero[1024 * 4] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_bucket_stamps), zero, sizeof(zero)) != hipSuccess) return DV_ERR_HIP;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_bucket_launch), zero, 4 * 8) != hipSuccess) return DV_ERR_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bucket_ctx), zero, kStampSlots * 8 * 8) != hipSuccess) return DV_ERR_HIP;
     return DV_OK;
 }
 #endif
 
-__global__ __launch_bounds__(kBucketThreads) void k_bucket_sort(uint64_t *__restrict__ in, uint64_t *__restrict__ out,
-                                                                const uint32_t *__restrict__ digit_tot,
-                                                                uint32_t hmul, int hbits, int hi_bits) {
+__global__ __launch_bounds__(kBucketThreads, kBucketWavesPerSimd) void k_bucket_sort(
+    uint64_t *__restrict__ in, uint64_t *__restrict__ out, const uint32_t *__restrict__ digit_tot,
+    const uint32_t *__restrict__ digit_pre, uint32_t hmul, int hbits, int hi_bits) {
 #ifdef DVCC_BUCKET_STAMPS
     BucketStamp stamp_;
     struct StampAtExit {
         BucketStamp &s;
         uint32_t b, m;
-        __device__ ~StampAtExit() { s.done(b, m); }
-    } stamp_exit_{stamp_, blockIdx.x, 0u};
+        const void *key;
+        __device__ ~StampAtExit() { s.done(b, m, key); }
+    } stamp_exit_{stamp_, blockIdx.x, 0u, digit_tot};
 #endif
-    __shared__ uint32_t tg[2][kBucketCap];
+    __shared__ uint32_t tg[kBucketCap];
     __shared__ uint32_t wc[kBucketWaves][kRadix];
     __shared__ uint32_t tot[kRadix], run[kRadix];
-    __shared__ uint32_t s_part[kBucketWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-    {  // the bucket's offset: the sizes of the buckets before it (gridDim.x <= kBucketThreads)
-        uint32_t v = tid < b ? digit_tot[tid] : 0u;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) s_part[wave] = v;
-    }
-    __syncthreads();
-    uint32_t base = 0;
-#pragma unroll
-    for (int w = 0; w < kBucketWaves; w++) base += s_part[w];
-    const uint32_t m = digit_tot[b];
+    // the bucket's size and its offset (the sizes of the buckets before it:
+    // written by the scatter's first tile, which scans the digit totals anyway)
+    const uint32_t m = digit_tot[b], base = digit_pre[b];
 #ifdef DVCC_BUCKET_STAMPS
     stamp_exit_.m = m;
 #endif
@@ -906,32 +955,36 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_sort(uint64_t *__rest
     const int passes = (hi_bits + kRadixBits - 1) / kRadixBits;
     const uint32_t hmask = (1u << hi_bits) - 1u;
     if (m <= kBucketCap) {
-        {  // every key's load in flight at once (a loop would wait on each)
-            uint64_t kv[kBucketSteps];
+        // a group of steps at a time, every key's load of the group in flight
+        // at once (a loop would wait on each)
+#pragma unroll 1
+        for (uint32_t g0 = 0; g0 < m; g0 += kBucketGroup * kBucketThreads) {
+            uint64_t kv[kBucketGroup];
 #pragma unroll
-            for (int s = 0; s < kBucketSteps; s++) {
-                const uint32_t i = s * kBucketThreads + tid;
+            for (int s = 0; s < kBucketGroup; s++) {
+                const uint32_t i = g0 + s * kBucketThreads + tid;
                 kv[s] = i < m ? in[base + i] : 0ull;
             }
 #pragma unroll
-            for (int s = 0; s < kBucketSteps; s++) {
-                const uint32_t i = s * kBucketThreads + tid;
-                if (i < m) tg[0][i] = ((row_hash(kv[s], hmul, hbits) & hmask) << kBucketIdxBits) | i;
+            for (int s = 0; s < kBucketGroup; s++) {
+                const uint32_t i = g0 + s * kBucketThreads + tid;
+                if (i < m) tg[i] = ((row_hash(kv[s], hmul, hbits) & hmask) << kBucketIdxBits) | i;
             }
         }
         __syncthreads();
         const uint32_t steps = (m + kBucketThreads - 1) / kBucketThreads;
-        int cur = 0;
         for (int p = 0; p < passes; p++) {
             const int sh = kBucketIdxBits + kRadixBits * p;
             for (uint32_t d = lane; d < (uint32_t)kRadix; d += 64) wc[wave][d] = 0;
+            // every tag of the thread is read (and ranked) before the barrier
+            // and written back after it: the scatter goes into the same array
             uint32_t t[kBucketSteps], r[kBucketSteps];
 #pragma unroll
             for (int s = 0; s < kBucketSteps; s++) {
                 if ((uint32_t)s < steps) {
                     const uint32_t e = (wave * steps + s) * 64 + lane;
                     const bool valid = e < m;
-                    t[s] = valid ? tg[cur][e] : 0u;
+                    t[s] = valid ? tg[e] : 0u;
                     r[s] = bucket_rank((t[s] >> sh) & (kRadix - 1), valid, wc[wave], lane);
                 }
             }
@@ -941,27 +994,30 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_sort(uint64_t *__rest
             for (int s = 0; s < kBucketSteps; s++) {
                 if ((uint32_t)s < steps) {
                     const uint32_t e = (wave * steps + s) * 64 + lane;
-                    if (e < m) tg[cur ^ 1][wc[wave][(t[s] >> sh) & (kRadix - 1)] + r[s]] = t[s];
+                    if (e < m) tg[wc[wave][(t[s] >> sh) & (kRadix - 1)] + r[s]] = t[s];
                 }
             }
             __syncthreads();
-            cur ^= 1;
         }
-        uint64_t kv[kBucketSteps];
+#pragma unroll 1
+        for (uint32_t g0 = 0; g0 < m; g0 += kBucketGroup * kBucketThreads) {
+            uint64_t kv[kBucketGroup];
 #pragma unroll
-        for (int s = 0; s < kBucketSteps; s++) {
-            const uint32_t i = s * kBucketThreads + tid;
-            kv[s] = i < m ? in[base + (tg[cur][i] & (kBucketCap - 1))] : 0ull;
-        }
+            for (int s = 0; s < kBucketGroup; s++) {
+                const uint32_t i = g0 + s * kBucketThreads + tid;
+                kv[s] = i < m ? in[base + (tg[i] & (kBucketCap - 1))] : 0ull;
+            }
 #pragma unroll
-        for (int s = 0; s < kBucketSteps; s++) {
-            const uint32_t i = s * kBucketThreads + tid;
-            if (i < m) out[base + i] = kv[s];
+            for (int s = 0; s < kBucketGroup; s++) {
+                const uint32_t i = g0 + s * kBucketThreads + tid;
+                if (i < m) out[base + i] = kv[s];
+            }
         }
         return;
     }
     // a bucket larger than the LDS: the same passes over global memory, the
-    // bucket's region of `in` as scratch
+    // bucket's region of `in` as scratch, in chunks of kBucketGroup steps
+    constexpr uint32_t kChunk = kBucketGroup * kBucketThreads;
     uint64_t *A = in + base, *B = out + base;
     for (int p = 0; p < passes; p++) {
         const uint64_t *src = (p & 1) ? B : A;
@@ -997,14 +1053,14 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_sort(uint64_t *__rest
             }
         }
         __syncthreads();
-        for (uint32_t c0 = 0; c0 < m; c0 += kBucketCap) {
-            const uint32_t mc = m - c0 < kBucketCap ? m - c0 : kBucketCap;
+        for (uint32_t c0 = 0; c0 < m; c0 += kChunk) {
+            const uint32_t mc = m - c0 < kChunk ? m - c0 : kChunk;
             const uint32_t steps = (mc + kBucketThreads - 1) / kBucketThreads;
             for (uint32_t d = lane; d < (uint32_t)kRadix; d += 64) wc[wave][d] = 0;
-            uint64_t k[kBucketSteps];
-            uint32_t r[kBucketSteps];
+            uint64_t k[kBucketGroup];
+            uint32_t r[kBucketGroup];
 #pragma unroll
-            for (int s = 0; s < kBucketSteps; s++) {
+            for (int s = 0; s < kBucketGroup; s++) {
                 if ((uint32_t)s < steps) {
                     const uint32_t e = (wave * steps + s) * 64 + lane;
                     const bool valid = e < mc;
@@ -1016,7 +1072,7 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_sort(uint64_t *__rest
             __syncthreads();
             bucket_bases(wc, tot, run);
 #pragma unroll
-            for (int s = 0; s < kBucketSteps; s++) {
+            for (int s = 0; s < kBucketGroup; s++) {
                 if ((uint32_t)s < steps) {
                     const uint32_t e = (wave * steps + s) * 64 + lane;
                     if (e < mc) dst[wc[wave][((row_hash(k[s], hmul, hbits) & hmask) >> sh) & (kRadix - 1)] + r[s]] = k[s];
@@ -1039,20 +1095,21 @@ int radix_sort_rows(hipStream_t s, uint64_t *pairs[2], uint64_t n, int key_bits,
     if (!lsd_only && bucket_sort_applies(n, key_bits, hist0_done, n_dev != nullptr)) {
         const int lo = kBucketLoBits(key_bits);
         const uint32_t hmul = kRowHashMul;
+        uint32_t *digit_pre = digit_tot + kRadixMax;  // the buckets' offsets (the scatter's first tile writes them)
         hipEvent_t e0 = scatter_ev ? scatter_ev[0] : nullptr, e1 = scatter_ev ? scatter_ev[1] : nullptr;
         if (lo == 9)
-            wide_pass<9>(s, pairs[0], pairs[1], n, 32, counts, digit_tot, nb, n_dev, e0, e1, hmul, key_bits);
+            wide_pass<9>(s, pairs[0], pairs[1], n, 32, counts, digit_tot, nb, n_dev, e0, e1, hmul, key_bits, digit_pre);
         else if (lo == 10)
-            wide_pass<10>(s, pairs[0], pairs[1], n, 32, counts, digit_tot, nb, n_dev, e0, e1, hmul, key_bits);
+            wide_pass<10>(s, pairs[0], pairs[1], n, 32, counts, digit_tot, nb, n_dev, e0, e1, hmul, key_bits, digit_pre);
         else {
             DV_LAUNCH(k_radix_hist, nb, kBlock, 0, s, pairs[0], n, 32, counts, nb, n_dev, hmul, key_bits);
             DV_LAUNCH(k_radix_scan, kRadix, kBlock, 0, s, counts, nb, digit_tot, n_dev);
             DV_LAUNCH_EV(k_radix_scatter, nb, kBlock, 0, s, e0, e1, (const uint64_t *)pairs[0], pairs[1], n, 32,
-                         (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, hmul, key_bits);
+                         (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, hmul, key_bits, digit_pre);
         }
         DV_LAUNCH_EV(k_bucket_sort, 1u << lo, kBucketThreads, 0, s, scatter_ev ? scatter_ev[2] : nullptr,
                      scatter_ev ? scatter_ev[3] : nullptr, pairs[1], pairs[0], (const uint32_t *)digit_tot,
-                     hmul, key_bits, key_bits - lo);
+                     (const uint32_t *)digit_pre, hmul, key_bits, key_bits - lo);
         return 0;
     }
     const int wbits = radix_digit_bits(key_bits, hist0_done);
@@ -1075,7 +1132,7 @@ int radix_sort_rows(hipStream_t s, uint64_t *pairs[2], uint64_t n, int key_bits,
         // timing: events recorded by the dispatch itself (no extra packets)
         DV_LAUNCH_EV(k_radix_scatter, nb, kBlock, 0, s, scatter_ev ? scatter_ev[2 * pass] : nullptr,
                      scatter_ev ? scatter_ev[2 * pass + 1] : nullptr, (const uint64_t *)pairs[cur], pairs[cur ^ 1], n,
-                     shift, (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, 0u, 0);
+                     shift, (const uint32_t *)counts, (const uint32_t *)digit_tot, nb, n_dev, 0u, 0, (uint32_t *)nullptr);
         cur ^= 1;
     }
     return cur;

@@ -786,7 +786,7 @@ int dv_open(dv_ctx **out, const dv_config *cfg) {
     if (!r) r = dalloc(&c->pairs[0], A);
     if (!r) r = dalloc(&c->pairs[1], A);
     if (!r) r = dalloc(&c->counts, (uint64_t)kRadixMax * nb);
-    if (!r) r = dalloc(&c->digit_tot, kRadixMax);
+    if (!r) r = dalloc(&c->digit_tot, 2 * kRadixMax);  // (totals, then a bucket sort's offsets)
     if (!r) r = dalloc(&c->status, c->n_txn_cap_pad);
     if (!r) r = dalloc(&c->verdict, c->n_txn_cap_pad);
     if (!r) r = dalloc(&c->ctr, 1);
