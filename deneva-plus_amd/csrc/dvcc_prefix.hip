@@ -75,8 +75,11 @@ static_assert((kHotWords + kBloomWords) * sizeof(uint32_t) <= 160u * 1024u,
               "k_kill's hot row words + Bloom filter exceed gfx950's 160 KiB of LDS per workgroup");
 __device__ __forceinline__ uint32_t bloom_bit(uint32_t row) { return (row * 0x9E3779B1u) >> (32 - DVCC_BLOOM_LOG); }
 
-// (a multiple of 4 words: k_epoch_clear zeroes it in 16-byte stores)
-uint64_t row_state_words(uint64_t rows) { return (((rows + 15) / 16 + 3) & ~3ull) + kBloomWords; }
+// (a multiple of 4 words: k_epoch_clear zeroes it in 16-byte stores; never
+// shorter than the hot rows' words, so k_kill's LDS fill needs no bound)
+uint64_t row_state_words(uint64_t rows) {
+    return std::max<uint64_t>(((rows + 15) / 16 + 3) & ~3ull, kHotWords) + kBloomWords;
+}
 
 // the rows of the committed prefix txns into the bitmap; lane per txn, its
 // accesses from the probe's txn-major acc_row (or the epoch's own records,
@@ -160,15 +163,19 @@ __global__ __launch_bounds__(kMarkBlock) void k_prefix_mark(uint8_t *__restrict_
 
 // Every access after the prefix's (index >= ctr->a_acc) against the row
 // state, one bit per access: 64 consecutive accesses per wave step, the
-// txn-major acc_row streamed (4 B per access), one bitmap word gathered per
-// access, and the wave's verdicts stored as one ballot word -- k_kill_compact
-// then ORs each txn's range of bits.  (The conflict rule is the one in the
+// txn-major acc_row streamed (4 B per access), one state word read per
+// access (LDS, or a gather from L2: below), and the wave's verdicts stored as
+// ballot words, word q of a step by lane q -- k_kill_count / k_kill_emit then
+// read each txn's range of bits.  (The conflict rule is the one in the
 // header comment; the txn id of an access is never needed here.)
 #ifndef DVCC_KILL_WORDS
 #define DVCC_KILL_WORDS 8
 #endif
 constexpr int kKillWords = DVCC_KILL_WORDS;  // ballot words per wave per step (loads in flight)
 constexpr int kKillBlock = 1024;  // one block per CU (144 KiB of LDS): 16 waves to stream with
+#ifndef DVCC_KILL_GRID
+#define DVCC_KILL_GRID 256  // (blocks at most: the chip's CUs, on a 64-CU decision lane as well)
+#endif
 // KEYS (an epoch with its txn boundaries, launch_probe_tb): the later
 // accesses were never probed -- their rows come from their keys here (the
 // dense YCSB map: arithmetic only), 9 bytes read per access instead of the
@@ -176,97 +183,123 @@ constexpr int kKillBlock = 1024;  // one block per CU (144 KiB of LDS): 16 waves
 template <int KEYS>  // 0: acc_row; 1: keys, probed; 2: keys of a dense map (KillKeys::dense_lim)
 __global__ __launch_bounds__(kKillBlock) void k_kill(const uint32_t *__restrict__ acc_row, uint64_t n,
                                                  const uint32_t *__restrict__ n_dev,
-                                                 const uint32_t *__restrict__ row_state, uint64_t state_words,
+                                                 const uint32_t *__restrict__ row_state,
                                                  const uint32_t *__restrict__ bloom, int nowait,
                                                  uint64_t *__restrict__ kill_bits, uint64_t *__restrict__ skip_bits,
                                                  Counters *__restrict__ ctr, KillKeys kk) {
     __shared__ __align__(16) uint32_t s_lds[kHotWords + kBloomWords];
-    uint32_t *const s_hot = s_lds, *const s_bloom = s_lds + kHotWords;
-    if (input_err(ctr) || ctr->halt) return;
-    if (n_dev && (uint64_t)*n_dev < n) n = *n_dev;  // (rows past the real count were never probed)
+    // everything the block needs from the counters in one round trip (n_dev:
+    // the epoch's real access count, rows past it were never probed; a null
+    // n_dev reads a_acc again and the word is not used)
+    const uint32_t err = ctr->err | ctr->peer_err, halt = ctr->halt, a_acc = ctr->a_acc;
+    const uint32_t n_real = *(n_dev ? n_dev : &ctr->a_acc);
+    asm volatile("" ::"s"(err), "s"(halt), "s"(a_acc), "s"(n_real));  // (all four loaded before the first branch)
+    if ((err & ERRB_INPUT) || halt) return;
+    if (n_dev && (uint64_t)n_real < n) n = n_real;
+    if (!n) return;
+    const uint64_t first = a_acc;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t w0 = first >> 6, nw = (n + 63) >> 6;
+    const uint64_t waves = (uint64_t)gridDim.x * (kKillBlock / 64);
+    const uint64_t wstep = waves * kKillWords;
+    const uint64_t wbeg = w0 + ((uint64_t)blockIdx.x * (kKillBlock / 64) + (threadIdx.x >> 6)) * kKillWords;
+    // the records loop's 4-byte words of a step (acc_row, or the dense map's
+    // records): no branch around a load -- the index clamped into [0, n), a
+    // word outside [first, n) dropped where it is used, a step later -- so
+    // the eight go out together and a wait for loads issued before them
+    // leaves them in flight
+    const bool rec_loop = KEYS == 0 || (KEYS == 2 && kk.recs);
+    const uint32_t *src = KEYS == 0 ? acc_row : kk.recs;
+    uint32_t nxt[kKillWords];
+    auto load = [&](uint64_t w) {
+#pragma unroll
+        for (int q = 0; q < kKillWords; q++) {
+            const uint64_t i = ((w + q) << 6) + lane;
+            nxt[q] = src[i < n ? i : n - 1];
+        }
+    };
+    if (rec_loop) load(wbeg);  // (the first step's, behind the LDS fill)
     {
         // the 144 KiB in 16-byte loads, all of a thread's in flight before its
         // first LDS store (a load-store loop waited out one L2 round trip per
-        // 4 KiB); the bitmap part and the filter are multiples of 4 words
+        // 4 KiB); the bitmap part (row_state_words: at least the hot rows'
+        // words) and the filter are multiples of 4 words
         constexpr uint32_t kH4 = kHotWords / 4, kAll4 = (kHotWords + kBloomWords) / 4;
         static_assert(kAll4 % kKillBlock == 0, "k_kill's LDS fill: whole 16-byte steps per thread");
         constexpr uint32_t kSteps = kAll4 / kKillBlock;
-        const uint32_t sw4 = (uint32_t)(state_words / 4 < kH4 ? state_words / 4 : kH4);
         const uint4 *hot4 = reinterpret_cast<const uint4 *>(row_state);
         const uint4 *blm4 = reinterpret_cast<const uint4 *>(bloom);
         uint4 v[kSteps];
 #pragma unroll
         for (uint32_t k = 0; k < kSteps; k++) {
             const uint32_t i = k * kKillBlock + threadIdx.x;
-            v[k] = i < kH4 ? (i < sw4 ? hot4[i] : make_uint4(0u, 0u, 0u, 0u)) : blm4[i - kH4];
+            v[k] = *(i < kH4 ? hot4 + i : blm4 + (i - kH4));
         }
         uint4 *dst = reinterpret_cast<uint4 *>(s_lds);
 #pragma unroll
         for (uint32_t k = 0; k < kSteps; k++) dst[k * kKillBlock + threadIdx.x] = v[k];
     }
     __syncthreads();
-    const uint64_t first = ctr->a_acc;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t w0 = first >> 6, nw = (n + 63) >> 6;
-    const uint64_t waves = (uint64_t)gridDim.x * (kKillBlock / 64);
-    const uint64_t wstep = waves * kKillWords;
-    // the state words of a step's accesses -- LDS (hot rows; the filter) or, a
-    // filter hit, the bitmap word from L2, all of the step's gathers in flight
-    // together -- then the verdicts
-    auto states = [&](const uint32_t *ar, uint32_t *sw) {
+    // The state words of a step's accesses, in two address spaces, each batch
+    // in flight at once.  lds_words: one word of the LDS array per slot,
+    // unconditionally -- a hot row's bitmap word, a cold row's filter word
+    // (word 0 for an empty slot).  gathers: the bitmap word from L2 for the
+    // cold slots whose filter bit is set, through the global pointer.  The
+    // two meet as values only (the select in verdicts): a select between an
+    // LDS and a global pointer compiles to one FLAT load per slot, which
+    // counts on both wait counters and is waited for slot by slot -- eight
+    // LDS and L2 round trips in sequence per step instead of one of each.
+    auto lds_words = [&](const uint32_t *ar, uint32_t *lw) {
 #pragma unroll
         for (int q = 0; q < kKillWords; q++) {
-            sw[q] = 0;
-            if (ar[q] != ~0u) {
-                const uint32_t row = ar[q] & ~AR_WR;
-                if (row < kHotRows) {
-                    sw[q] = s_hot[row >> 4];
-                } else {
-                    const uint32_t h = bloom_bit(row);
-                    if ((s_bloom[h >> 5] >> (h & 31u)) & 1u) sw[q] = row_state[row >> 4];  // maybe marked
-                }
-            }
+            const uint32_t row = ar[q] & ~AR_WR;
+            const uint32_t idx = row < kHotRows ? row >> 4 : kHotWords + (bloom_bit(row) >> 5);
+            lw[q] = s_lds[ar[q] != ~0u ? idx : 0u];
         }
     };
-    auto verdicts = [&](uint64_t w, const uint32_t *ar, const uint32_t *sw) {
+    auto gathers = [&](const uint32_t *ar, const uint32_t *lw, uint32_t *gw) {
 #pragma unroll
         for (int q = 0; q < kKillWords; q++) {
-            bool kill = false, skip = false;
-            if (ar[q] != ~0u) {
-                const uint32_t row = ar[q] & ~AR_WR;
-                const uint32_t st = (sw[q] >> ((row & 15u) * 2u)) & 3u;
-                kill = (st & RS_WR) || (nowait && st && (ar[q] & AR_WR));
-                skip = st == RS_RD && !(ar[q] & AR_WR);  // (nowait only: skip_bits is null for OCC)
-            }
-            const uint64_t m = __ballot(kill), sm = __ballot(skip);
-            if (lane == 0 && w + q < nw) {
-                kill_bits[w + q] = m;
-                if (skip_bits) skip_bits[w + q] = sm;
-            }
+            const uint32_t row = ar[q] & ~AR_WR;
+            gw[q] = 0;
+            if (ar[q] != ~0u && row >= kHotRows && ((lw[q] >> (bloom_bit(row) & 31u)) & 1u))
+                gw[q] = row_state[row >> 4];  // maybe marked
         }
     };
-    const uint64_t wbeg = w0 + ((uint64_t)blockIdx.x * (kKillBlock / 64) + (threadIdx.x >> 6)) * kKillWords;
-    if (KEYS == 0 || (KEYS == 2 && kk.recs)) {
-        // one 4-byte word per access (acc_row, or the dense map's records):
-        // software-pipelined -- the next step's words are loaded behind this
-        // step's gathers, so the stream's latency overlaps the verdicts
-        const uint32_t *src = KEYS == 0 ? acc_row : kk.recs;
-        uint32_t nxt[kKillWords];
-        auto load = [&](uint64_t w) {
+    // (an empty slot needs no test here: its row is no hot row and its gather
+    // word is 0, state 00.)  Ballot word q of the step moves to lane q, and
+    // each array is stored once per step: a store per word, issued between
+    // the verdicts, would count on the same counter as the prefetched records
+    // behind the gathers and make the later verdicts' waits drain them
+    auto verdicts = [&](uint64_t w, const uint32_t *ar, const uint32_t *lw, const uint32_t *gw) {
+        uint64_t km = 0, sm = 0;
+#pragma unroll
+        for (int q = 0; q < kKillWords; q++) {
+            const uint32_t row = ar[q] & ~AR_WR;
+            const uint32_t sw = row < kHotRows ? lw[q] : gw[q];
+            const uint32_t st = (sw >> ((row & 15u) * 2u)) & 3u;
+            const bool kill = (st & RS_WR) || (nowait && st && (ar[q] & AR_WR));
+            const bool skip = st == RS_RD && !(ar[q] & AR_WR);  // (nowait only: skip_bits is null for OCC)
+            const uint64_t m = __ballot(kill), s = __ballot(skip);
+            km = lane == (uint32_t)q ? m : km;
+            sm = lane == (uint32_t)q ? s : sm;
+        }
+        if (lane < (uint32_t)kKillWords && w + lane < nw) {
+            kill_bits[w + lane] = km;
+            if (skip_bits) skip_bits[w + lane] = sm;
+        }
+    };
+    if (rec_loop) {
+        // one 4-byte word per access, software-pipelined: the step's gathers
+        // go out first, the next step's words behind them, and the verdicts
+        // wait for the gathers alone -- the stream's latency overlaps them
+        for (uint64_t w = wbeg; w < nw; w += wstep) {
+            uint32_t ar[kKillWords], lw[kKillWords], gw[kKillWords];
 #pragma unroll
             for (int q = 0; q < kKillWords; q++) {
                 const uint64_t i = ((w + q) << 6) + lane;
-                nxt[q] = w < nw && i >= first && i < n ? src[i] : ~0u;
-            }
-        };
-        load(wbeg);
-        for (uint64_t w = wbeg; w < nw; w += wstep) {
-            uint32_t ar[kKillWords], sw[kKillWords];
-#pragma unroll
-            for (int q = 0; q < kKillWords; q++) {
-                ar[q] = nxt[q];
+                ar[q] = i >= first && i < n ? nxt[q] : ~0u;
                 if constexpr (KEYS == 2) {  // key | wr << 31 -> row | AR_WR (a missing key rejects the epoch)
-                    const uint64_t i = ((w + q) << 6) + lane;
                     if (i >= first && i < n) {
                         const uint32_t key = nxt[q] & 0x7FFFFFFFu;
                         if (key < kk.dense_lim) {
@@ -280,14 +313,15 @@ __global__ __launch_bounds__(kKillBlock) void k_kill(const uint32_t *__restrict_
                     }
                 }
             }
-            states(ar, sw);
+            lds_words(ar, lw);
+            gathers(ar, lw, gw);
             load(w + wstep);
-            verdicts(w, ar, sw);
+            verdicts(w, ar, lw, gw);
         }
         return;
     }
     for (uint64_t w = wbeg; w < nw; w += wstep) {
-        uint32_t ar[kKillWords], sw[kKillWords];
+        uint32_t ar[kKillWords], lw[kKillWords], gw[kKillWords];
         if constexpr (KEYS != 0) {
             uint64_t key[kKillWords];
             uint32_t wr[kKillWords];
@@ -307,8 +341,9 @@ __global__ __launch_bounds__(kKillBlock) void k_kill(const uint32_t *__restrict_
                     ar[q] = (uint32_t)row | (wr[q] ? AR_WR : 0u);
             }
         }
-        states(ar, sw);
-        verdicts(w, ar, sw);
+        lds_words(ar, lw);
+        gathers(ar, lw, gw);
+        verdicts(w, ar, lw, gw);
     }
 }
 
@@ -712,15 +747,15 @@ void launch_kill_compact(hipStream_t s, const uint32_t *tb_start, const uint32_t
     const KillKeys k0 = kk ? *kk : KillKeys{};
     uint32_t *ar = const_cast<uint32_t *>(acc_row);  // (k_kill_emit<1> writes the survivors')
     // (144 KiB of LDS per block: one per CU, each loads the hot words and the filter once)
-    const uint32_t kg = grid_of(nw * 64 / kKillWords / 4 + 1, 256);
+    const uint32_t kg = grid_of(nw * 64 / kKillWords / 4 + 1, DVCC_KILL_GRID);
     if (kk && k0.dense_lim)
-        DV_LAUNCH(k_kill<2>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state, rs_words - kBloomWords,
+        DV_LAUNCH(k_kill<2>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state,
                   row_state + (rs_words - kBloomWords), nowait, kill_bits, skip_bits, ctr, k0);
     else if (kk)
-        DV_LAUNCH(k_kill<1>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state, rs_words - kBloomWords,
+        DV_LAUNCH(k_kill<1>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state,
                   row_state + (rs_words - kBloomWords), nowait, kill_bits, skip_bits, ctr, k0);
     else
-        DV_LAUNCH(k_kill<0>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state, rs_words - kBloomWords,
+        DV_LAUNCH(k_kill<0>, kg, kKillBlock, 0, s, acc_row, n_acc, n_acc_dev, row_state,
                   row_state + (rs_words - kBloomWords), nowait, kill_bits, skip_bits, ctr, k0);
     DV_LAUNCH(k_kill_count, nt, kBlock, 0, s, tb_start, tb_end, K, n_txn, (const uint64_t *)kill_bits,
               (const uint64_t *)skip_bits, status, info, tsum, ctr);
