@@ -481,7 +481,10 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
 // in a ring of D slots, slot e % D holding what falls due in epoch e.  A
 // parked txn is its identity word and an abort count byte (9 bytes); its
 // accesses are read from the pool again when it is released.  The chain behind
-// epoch k (building epoch e = k + 1, all kernel boundaries, no flags):
+// epoch k (building epoch e = k + 1, all kernel boundaries, no flags; under L
+// decision lanes -- dv_closed_loop_backoff_lanes -- e = k + L, on epoch k's
+// lane, and the park's delays count from e - 1, so the a-th abort costs
+// L - 1 + min(2^(a-1), D) epochs; the chain is the same):
 //   k_bo_count   per 256-txn carry block and delay class, the aborts
 //   k_bo_scan    a workgroup per class: exclusive scan over the blocks
 //   k_bo_plan    one thread: the skip word; per class its slot and the slot's
@@ -567,8 +570,11 @@ __global__ __launch_bounds__(kBlock) void k_bo_scan(uint32_t *__restrict__ c, ui
     if (threadIdx.x == 0) totals[blockIdx.x] = tot;
 }
 
-// k: the epoch decided (prev: there is one), e: the epoch being built
-__global__ void k_bo_plan(int prev, uint32_t k, uint32_t e, uint32_t n_out, uint32_t *cursor, uint32_t pool_n,
+// e: the epoch being built; the ring's clock for the park before it is e - 1
+// (prev: an epoch was decided -- epoch e - L under L decision lanes, whose
+// aborts cannot return before e: the delays count from e - 1, and for one
+// lane e - 1 is the epoch decided)
+__global__ void k_bo_plan(int prev, uint32_t e, uint32_t n_out, uint32_t *cursor, uint32_t pool_n,
                           const Counters *ctr, uint32_t *tot, RefillBackoff bo) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint32_t skip = prev && refill_skip(ctr) ? 1u : 0u;
@@ -578,7 +584,7 @@ __global__ void k_bo_plan(int prev, uint32_t k, uint32_t e, uint32_t n_out, uint
     uint32_t aborted = 0;
     uint64_t lost = 0;
     for (uint32_t c = 0; prev && c <= bo.lgD; c++) {  // (the delays 1 .. D fall into distinct slots)
-        const uint32_t slot = (k + (1u << c)) & mask, n = bo.bw[BW_CTOT + c];
+        const uint32_t slot = (e - 1u + (1u << c)) & mask, n = bo.bw[BW_CTOT + c];
         const uint32_t base = bo.slot_count[slot] < bo.cap ? bo.slot_count[slot] : bo.cap;
         const uint64_t want = (uint64_t)base + n;
         const uint32_t now = want < bo.cap ? (uint32_t)want : bo.cap;
@@ -844,7 +850,7 @@ void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn,
         DV_LAUNCH(k_bo_count, nb, kBlock, 0, s, status, bo.aborts, n_txn, nb, bo.lgD, bo.cls);
         DV_LAUNCH(k_bo_scan, bo.lgD + 1, kBlock, 0, s, bo.cls, nb, bo.bw + BW_CTOT);
     }
-    DV_LAUNCH(k_bo_plan, 1, 64, 0, s, nb ? 1 : 0, trk.k, trk.k_next, n_out, cursor, pool_n, ctr, tot, bo);
+    DV_LAUNCH(k_bo_plan, 1, 64, 0, s, nb ? 1 : 0, trk.k_next, n_out, cursor, pool_n, ctr, tot, bo);
     if (nb) DV_LAUNCH(k_bo_park, (nb + wpb - 1) / wpb, kBlock, 0, s, status, n_txn, nb, tot, trk, bo);
     const uint32_t gs = (bo.cap + kBlock - 1) / kBlock;
     DV_LAUNCH(k_bo_spill, gs < 1 ? 1 : (gs > 1024 ? 1024 : gs), kBlock, 0, s, tot, bo);

@@ -644,7 +644,12 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
 // falls due, capped at n_out, then fresh pool txns; every txn's accesses are
 // read from the pool by its identity word's src.  A different launch chain
 // from launch_refill's (nothing is copied from the decided epoch), no-ops
-// under the same skip word tot[4].
+// under the same skip word tot[4].  Under L decision lanes
+// (dv_closed_loop_backoff_lanes) trk->k_next = trk->k + L and the ring's clock
+// for the park is trk->k_next - 1: an abort cannot return before epoch k + L.
+// The ring, the counters, wpart and lost are then lanes[0]'s, shared by the
+// lanes' refills (in epoch order on the device); cls, gb and bw are the
+// refilling lane's own.
 //   aborts / oaborts: the abort counts of the decided epoch and of the one
 //     being built; cls: kBoClasses x carry_blocks(n_txn) per-block class
 //     counts; gb: carry_blocks(n_out) per-block access counts; bw: kBoWords

@@ -160,15 +160,20 @@ struct dv_ctx {
         uint32_t next = 0;
     } trk;
     uint32_t *trk_part = nullptr;  // RefillTrack::part (allocated by the first attachment, zero between refills)
-    // dv_closed_loop_backoff: the attached ring (its struct and aborts pointers
-    // copied), and the refill's workspace for bo_nb carry blocks -- the wait
-    // partials and the context's own lost count (8-byte words, first), the plan
-    // words, the class and gather block counts (RefillBackoff); lost_seen: that
-    // count as the last loop call read it
+    // dv_closed_loop_backoff / dv_closed_loop_backoff_lanes: the attached ring
+    // (its struct and aborts pointers copied; lanes: the lane count it was
+    // attached for, 1 through the first entry), and the refill's workspace for
+    // bo_nb carry blocks -- the wait partials and the context's own lost count
+    // (8-byte words, first), the plan words, the class and gather block counts
+    // (RefillBackoff); lost_seen: that count as the last loop call read it.
+    // Under decision lanes the ring, the wait partials and the lost count are
+    // lanes[0]'s, and every lane brings its own plan words and block counts
+    // (backoff_at).
     struct LoopBo {
         bool on = false;
+        uint32_t lanes = 1;
         dv_loop_backoff t{};
-        uint8_t *aborts[2] = {nullptr, nullptr};
+        uint8_t *aborts[2 * kMaxLanes] = {};
         unsigned long long lost_seen = 0;
     } bo;
     uint32_t *bo_ws = nullptr;
@@ -3159,9 +3164,17 @@ const RefillTrack *track_at(const dv_ctx *t, bool prev, uint32_t k, uint32_t k_n
     return w;
 }
 // The back-off ring (dv_closed_loop_backoff) of context t for the same refill
-// (ib / ob: the decided and the built epoch's buffers).  NULL when nothing is
-// attached.
-const RefillBackoff *backoff_at(const dv_ctx *t, uint32_t ib, uint32_t ob, RefillBackoff *w) {
+// (ib / ob: the decided and the built epoch's buffers), queued on context c
+// (t itself, or one of the lanes t leads).  NULL when nothing is attached.
+// What outlives a refill -- the ring, the counters, the wait partials, the
+// lost count -- is t's; the words a refill only passes from one of its kernels
+// to the next (bw, cls, gb) are c's own.  The lanes' refills run in epoch
+// order on the device (k_lane_wait, execution, refill, k_lane_post), so t's
+// words have one writer at a time; k_bo_count and the two k_bo_scan write
+// before the skip word is known or without reading it, which is why they get
+// the lane's words: a lane halted by its wait's time limit cannot touch what
+// the refill still running on the lane before it reads.
+const RefillBackoff *backoff_at(const dv_ctx *t, const dv_ctx *c, uint32_t ib, uint32_t ob, RefillBackoff *w) {
     if (!t->bo.on) return nullptr;
     const dv_loop_backoff &d = t->bo.t;
     w->D = d.n_slots;
@@ -3176,14 +3189,16 @@ const RefillBackoff *backoff_at(const dv_ctx *t, uint32_t ib, uint32_t ob, Refil
     unsigned long long *w64 = reinterpret_cast<unsigned long long *>(t->bo_ws);
     w->wpart = w64;
     w->lost = w64 + kTrackSlots;
-    w->bw = t->bo_ws + 2 * (kTrackSlots + 1);
+    w->bw = c->bo_ws + 2 * (kTrackSlots + 1);
     w->cls = w->bw + kBoWords;
-    w->gb = w->cls + (size_t)kBoClasses * t->bo_nb;
+    w->gb = w->cls + (size_t)kBoClasses * c->bo_nb;
     return w;
 }
-// the back-off workspace for nb carry blocks (zeroed when allocated)
-int backoff_bufs(dv_ctx *c, uint32_t nb) {
-    if (!c->bo.on || (c->bo_ws && nb <= c->bo_nb)) return DV_OK;
+// the back-off workspace of context c for nb carry blocks (zeroed when
+// allocated); on: a back-off is attached to the loop (to c, or to the first
+// of its lanes)
+int backoff_bufs(dv_ctx *c, uint32_t nb, bool on) {
+    if (!on || (c->bo_ws && nb <= c->bo_nb)) return DV_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
     dfree(c->bo_ws);
     c->bo_ws = nullptr;
@@ -3197,6 +3212,17 @@ int backoff_bufs(dv_ctx *c, uint32_t nb) {
     return DV_OK;
 }
 // a loop call over n_bufs buffers and n_epochs epochs against the attachment
+// the call's lost entries (capacity exceeded: counted in
+// dv_loop_backoff::counters[1], not written), read once after its last epoch
+int backoff_lost(dv_ctx *c) {
+    if (!c->bo.on) return DV_OK;
+    unsigned long long lost = 0;
+    HIPCHK(hipMemcpy(&lost, reinterpret_cast<unsigned long long *>(c->bo_ws) + kTrackSlots, sizeof(lost),
+                     hipMemcpyDeviceToHost));
+    const bool more = lost != c->bo.lost_seen;
+    c->bo.lost_seen = lost;
+    return more ? DV_ERR_ARG : DV_OK;
+}
 int track_check(const dv_ctx *t, uint32_t n_bufs, uint32_t n_epochs) {
     if (!t->trk.on) return DV_OK;
     const dv_loop_track &d = t->trk.t;
@@ -3215,6 +3241,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     if (!c || !pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
     if (c->cfg.cc_alg == DV_CALVIN || c->cfg.workload != DV_YCSB || c->comm) return DV_ERR_STATE;
+    if (c->bo.on && c->bo.lanes != 1) return DV_ERR_STATE;  // (a ring attached for the lanes loop)
     const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
     if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
         bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn)
@@ -3226,7 +3253,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     int r = carry_bufs(c, carry_blocks(n_txn));
-    if (!r) r = backoff_bufs(c, carry_blocks(n_txn));
+    if (!r) r = backoff_bufs(c, carry_blocks(n_txn), c->bo.on);
     if (r) return r;
     const LoopForm form = loop_form(c, pool, bufs, 2, n_txn);
     RefillTrack tw;
@@ -3251,7 +3278,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     };
     if (!resume)
         enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, bufs[0], form,
-                       track_at(c, false, 0, 0, 0, 0, 1, &tw), backoff_at(c, 0, 0, &bw));
+                       track_at(c, false, 0, 0, 0, 0, 1, &tw), backoff_at(c, c, 0, 0, &bw));
     const dv_epoch_dev d0 = desc(0);
     const bool pipelined = prefix_applies(c, &d0) && !timing(c) && !ktiming(c) && !c->rep_P;
     EpochSnap snap[2];
@@ -3263,7 +3290,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
         if (!e) {
             enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
                            track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
-                           backoff_at(c, k & 1, (k + 1) & 1, &bw));
+                           backoff_at(c, c, k & 1, (k + 1) & 1, &bw));
             e = hip_fail(hipGetLastError(), "refill");
         }
         return e;
@@ -3282,7 +3309,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
             // no-op when k halted -- the host redoes both below)
             enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
                            track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
-                           backoff_at(c, k & 1, (k + 1) & 1, &bw));
+                           backoff_at(c, c, k & 1, (k + 1) & 1, &bw));
             r = hip_fail(hipGetLastError(), "refill");
         }
         if (r) {
@@ -3324,15 +3351,7 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
     c->trk.next += c->trk.on ? n_epochs : 0u;
-    if (c->bo.on) {  // capacity exceeded in this call: entries were dropped (counted, dv_loop_backoff::counters[1])
-        unsigned long long lost = 0;
-        HIPCHK(hipMemcpy(&lost, reinterpret_cast<unsigned long long *>(c->bo_ws) + kTrackSlots, sizeof(lost),
-                         hipMemcpyDeviceToHost));
-        const bool more = lost != c->bo.lost_seen;
-        c->bo.lost_seen = lost;
-        if (more) return DV_ERR_ARG;
-    }
-    return DV_OK;
+    return backoff_lost(c);
 }
 
 // The TPC-C closed loop: one epoch at a time -- decided (a halted decision is
@@ -3351,7 +3370,7 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
         c->cfg.workload != DV_TPCC)
         return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
-    if (c->cfg.cc_alg == DV_CALVIN || c->comm || c->bo.on) return DV_ERR_STATE;  // (bo: the single YCSB loop only)
+    if (c->cfg.cc_alg == DV_CALVIN || c->comm || c->bo.on) return DV_ERR_STATE;  // (bo: the YCSB loops only)
     const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
     if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
         bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn || !pool->tables)
@@ -3426,9 +3445,12 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
                                         d_commits, sts);
     if (!pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
     dv_ctx *const c0 = lanes[0];
+    KProfScope kps_(c0);  // (DV_FLAG_KERNEL_PROFILE on lanes[0]: every lane's refill launches are timed into it)
     if (c0->cfg.cc_alg == DV_CALVIN || c0->cfg.workload != DV_YCSB) return DV_ERR_STATE;
-    for (uint32_t l = 0; l < n_lanes; l++)
-        if (lanes[l]->bo.on) return DV_ERR_STATE;  // (a ring per lane: not built)
+    // a back-off: lanes[0]'s, attached for this lane count (dv_closed_loop_backoff_lanes)
+    if (c0->bo.on && c0->bo.lanes != n_lanes) return DV_ERR_STATE;
+    for (uint32_t l = 1; l < n_lanes; l++)
+        if (lanes[l]->bo.on) return DV_ERR_STATE;
     const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
     if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c0->cfg.max_txn || bound > buf_cap ||
         bound > c0->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn)
@@ -3443,6 +3465,7 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     HIPCHK(hipSetDevice(c0->cfg.device));
     for (uint32_t l = 0; l < n_lanes; l++) {
         r = carry_bufs(lanes[l], carry_blocks(n_txn));
+        if (!r) r = backoff_bufs(lanes[l], carry_blocks(n_txn), c0->bo.on);
         if (r) return r;
     }
     const LoopForm form = loop_form(c0, pool, bufs, 2 * n_lanes, n_txn);
@@ -3450,11 +3473,13 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     // 2l + (j & 1); its refill writes 2l + ((j + 1) & 1)
     auto buf_i = [&](uint32_t k, uint32_t ahead) { return 2 * (k % n_lanes) + (((k / n_lanes) + ahead) & 1); };
     auto buf_of = [&](uint32_t k, uint32_t ahead) { return &bufs[buf_i(k, ahead)]; };
-    // (the tracker is lanes[0]'s, shared: the refills run in epoch order)
+    // (the tracker and the back-off are lanes[0]'s, shared: the refills run in epoch order)
     RefillTrack tw;
+    RefillBackoff bw;
     auto track_of = [&](uint32_t k) {
         return track_at(c0, true, k, k + n_lanes, buf_i(k, 0), buf_i(k, 1), n_lanes, &tw);
     };
+    auto backoff_of = [&](dv_ctx *c, uint32_t k) { return backoff_at(c0, c, buf_i(k, 0), buf_i(k, 1), &bw); };
     auto desc = [&](uint32_t k) {
         dv_epoch_dev d = *buf_of(k, 0);
         if (form.old) d.txn_begin = d.recs32 = nullptr;  // (the engine reads the old form)
@@ -3466,11 +3491,12 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
         return d;
     };
     auto commit_of = [&](uint32_t k) { return d_commits ? d_commits[k] : nullptr; };
-    if (!resume)  // each lane's first epoch: fresh txns, drawn in lane order
+    if (!resume)  // each lane's first epoch: fresh txns (and what an attached ring releases), in lane order
         for (uint32_t l = 0; l < n_lanes; l++) {
             dv_ctx *c = lanes[l];
             enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, *buf_of(l, 0), form,
-                           track_at(c0, false, 0, l, 0, buf_i(l, 0), n_lanes, &tw));
+                           track_at(c0, false, 0, l, 0, buf_i(l, 0), n_lanes, &tw),
+                           backoff_at(c0, c, buf_i(l, 0), buf_i(l, 0), &bw));
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(c->stream));
         }
@@ -3485,7 +3511,8 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
         },
         [&](dv_ctx *c, uint32_t k) {  // (behind the execution; a no-op when k halted)
             const dv_epoch_dev d = desc(k);
-            enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form, track_of(k));
+            enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form, track_of(k),
+                           backoff_of(c, k));
             return hip_fail(hipGetLastError(), "refill");
         },
         [&](uint32_t k, dv_stats *st) {  // (synchronous, refill included: the next refill, on
@@ -3495,7 +3522,7 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
             int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, st);
             if (!e) {
                 enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form,
-                               track_of(k));
+                               track_of(k), backoff_of(c, k));
                 e = hip_fail(hipGetLastError(), "refill");
             }
             if (!e) e = hip_fail(hipStreamSynchronize(c->stream), "sync");
@@ -3503,7 +3530,7 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
         });
     for (uint32_t l = 0; l < n_lanes; l++) (void)hipStreamSynchronize(lanes[l]->stream);
     if (!r && c0->trk.on) c0->trk.next += n_epochs;
-    return r;
+    return r ? r : backoff_lost(c0);
 }
 
 int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
@@ -3534,26 +3561,29 @@ int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
     return DV_OK;
 }
 
-int dv_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) {
-    if (!c) return DV_ERR_ARG;
+int dv_closed_loop_backoff_lanes(dv_ctx *c, const dv_loop_backoff *bo, uint32_t n_lanes) {
+    if (!c || n_lanes == 0 || n_lanes > kMaxLanes) return DV_ERR_ARG;
     if (!bo) {
         c->bo.on = false;
         return DV_OK;
     }
     const uint32_t D = bo->n_slots;
     if ((D != 1 && D != 2 && D != 4 && D != 8 && D != 16) || !bo->slot_cap || !bo->park_ids || !bo->park_aborts ||
-        !bo->slot_count || !bo->aborts || !bo->aborts[0] || !bo->aborts[1] || !bo->counters ||
-        (uint64_t)D * bo->slot_cap > 0xFFFFFFFFull)
+        !bo->slot_count || !bo->aborts || !bo->counters || (uint64_t)D * bo->slot_cap > 0xFFFFFFFFull)
         return DV_ERR_ARG;
-    if (c->phase != 0 || c->cfg.cc_alg == DV_CALVIN || c->comm || !c->trk.on || c->trk.t.n_bufs != 2)
+    for (uint32_t b = 0; b < 2 * n_lanes; b++)
+        if (!bo->aborts[b]) return DV_ERR_ARG;
+    if (c->phase != 0 || c->cfg.cc_alg == DV_CALVIN || c->comm || !c->trk.on || c->trk.t.n_bufs != 2 * n_lanes)
         return DV_ERR_STATE;
     c->bo.on = true;
+    c->bo.lanes = n_lanes;
     c->bo.t = *bo;
-    c->bo.aborts[0] = bo->aborts[0];
-    c->bo.aborts[1] = bo->aborts[1];
+    for (uint32_t b = 0; b < 2 * kMaxLanes; b++) c->bo.aborts[b] = b < 2 * n_lanes ? bo->aborts[b] : nullptr;
     c->bo.t.aborts = nullptr;  // (the caller's array is not kept)
     return DV_OK;
 }
+
+int dv_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) { return dv_closed_loop_backoff_lanes(c, bo, 1); }
 
 }  // extern "C"
 

@@ -280,6 +280,7 @@ SIGNATURES = [
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
     ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
     ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
+    ("dv_closed_loop_backoff_lanes", ctypes.c_int, [_vp, _P(LoopBackoffDesc), ctypes.c_uint32]),
 ]
 
 _lib = None

@@ -351,35 +351,42 @@ class LoopTrack:
 
 
 class LoopBackoff:
-    """Exponential back-off for the single YCSB closed loop
-    (dv_closed_loop_backoff): a ring of n_slots slots of slot_cap parked txns
-    (identity word and abort count), the two epoch buffers' abort counts and
+    """Exponential back-off for the YCSB closed loops (dv_closed_loop_backoff,
+    dv_closed_loop_backoff_lanes): a ring of n_slots slots of slot_cap parked
+    txns (identity word and abort count), the epoch buffers' abort counts and
     the four counters -- device tensors this object owns.  Built over a
-    LoopTrack of two buffers; attach() it after the tracker, to the same
-    engine, and call swap() beside ClosedLoopBufs.swap and LoopTrack.swap.
-    slot_cap defaults to the bound n_txn * (D + log2 D), which no run
-    exceeds; detaching the tracker detaches the back-off."""
+    LoopTrack of two buffers (closed_loop) or of 2 L (closed_loop_lanes over L
+    contexts: one ring, shared by the lanes); attach() it after the tracker,
+    to the same engine, and for the single loop call swap() beside
+    ClosedLoopBufs.swap and LoopTrack.swap.  slot_cap defaults to the bound
+    n_txn * (D + log2 D), which no run exceeds; detaching the tracker detaches
+    the back-off."""
 
     def __init__(self, track, n_slots, slot_cap=None, device="cuda"):
         import torch
-        if track.n_bufs != 2:
-            raise ValueError("LoopBackoff: a single loop's two buffers only")
+        if track.n_bufs < 2 or track.n_bufs & 1:
+            raise ValueError("LoopBackoff: a tracker of two buffers, or two per lane")
         self.track, self.n_slots, self.n_txn = track, int(n_slots), track.n_txn
+        self.n_lanes = track.n_bufs // 2
         lg = max(0, self.n_slots.bit_length() - 1)
         self.slot_cap = int(slot_cap) if slot_cap is not None else self.n_txn * (self.n_slots + lg)
         z = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=device)  # noqa: E731
         n = max(1, self.n_slots) * self.slot_cap
         self.park_ids, self.park_aborts = z(n, torch.int64), z(n, torch.uint8)
         self.slot_count = z(max(1, self.n_slots), torch.int32)
-        self.aborts = [z(self.n_txn, torch.uint8) for _ in range(2)]
+        self.aborts = [z(self.n_txn, torch.uint8) for _ in range(2 * self.n_lanes)]
         self.ctr = z(4, torch.int64)
         self.engine = None
 
     def _attach(self):
-        arr = (ctypes.c_void_p * 2)(*[int(t.data_ptr()) for t in self.aborts])
+        arr = (ctypes.c_void_p * len(self.aborts))(*[int(t.data_ptr()) for t in self.aborts])
         d = L.LoopBackoffDesc(self.n_slots, self.slot_cap, self.park_ids.data_ptr(), self.park_aborts.data_ptr(),
                               self.slot_count.data_ptr(), arr, self.ctr.data_ptr())
-        L.check(L.lib().dv_closed_loop_backoff(self.engine._ctx, ctypes.byref(d)), "dv_closed_loop_backoff")
+        if self.n_lanes == 1:
+            L.check(L.lib().dv_closed_loop_backoff(self.engine._ctx, ctypes.byref(d)), "dv_closed_loop_backoff")
+        else:
+            L.check(L.lib().dv_closed_loop_backoff_lanes(self.engine._ctx, ctypes.byref(d), self.n_lanes),
+                    "dv_closed_loop_backoff_lanes")
 
     def attach(self, engine):
         """Backs off `engine`'s closed loop (its tracker attached first).  The
@@ -403,6 +410,8 @@ class LoopBackoff:
         """with ClosedLoopBufs.swap and LoopTrack.swap (call it after the
         tracker's), after a call of n_epochs odd: the next epoch's abort
         counts move to buffer 0 too"""
+        if self.n_lanes != 1:
+            raise ValueError("LoopBackoff.swap: a single loop's two buffers only")
         self.aborts.reverse()
         if self.engine is not None:
             self._attach()
@@ -931,7 +940,9 @@ class CCEngine:
         context k % L, each context's epochs a closed loop of their own
         (aborted txns retried L epochs later), the pool cursor shared.  bufs:
         one ClosedLoopBufs per context (allocated when None).  track: a
-        LoopTrack of 2 L buffers attached to this engine.  Returns (stats
+        LoopTrack of 2 L buffers attached to this engine (with a LoopBackoff
+        built over it and attached too, a txn's a-th abort costs
+        L - 1 + min(2^(a-1), D) epochs).  Returns (stats
         list, bufs, cursor); resume needs the previous call's n_epochs to be a
         multiple of 2 L."""
         import torch

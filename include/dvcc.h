@@ -631,9 +631,10 @@ int dv_closed_loop_track(dv_ctx *ctx, const dv_loop_track *trk);
  * Refused at attach time: a null context, array or aborts entry, n_slots not
  * 1, 2, 4, 8 or 16, slot_cap 0, a ring of 2^32 entries or more
  * (DV_ERR_ARG); no tracker, one of more than two buffers, a CALVIN context or
- * one with a communicator (DV_ERR_STATE).  With a back-off attached
- * dv_epoch_run_closed_loop_lanes (n_lanes > 1) and dv_tpcc_epoch_run_closed_loop
- * return DV_ERR_STATE before any launch.
+ * one with a communicator (DV_ERR_STATE).  With a back-off attached through
+ * this entry dv_epoch_run_closed_loop_lanes (n_lanes > 1) and
+ * dv_tpcc_epoch_run_closed_loop return DV_ERR_STATE before any launch (the
+ * lanes loop takes one attached through dv_closed_loop_backoff_lanes, below).
  * The refill is then a different chain (k_bo_count, k_bo_scan, k_bo_plan,
  * k_bo_park, k_bo_spill, k_bo_gather_count, k_bo_scan, k_bo_gather_copy,
  * k_bo_fold: dvcc_carry.hip), a no-op behind a halted or failed epoch like the
@@ -650,6 +651,54 @@ typedef struct dv_loop_backoff {
                                  (k - born), txns parked now (a level, stored not added)     */
 } dv_loop_backoff;
 int dv_closed_loop_backoff(dv_ctx *ctx, const dv_loop_backoff *bo);   /* NULL detaches */
+
+/* The back-off for the closed loop over decision lanes
+ * (dv_epoch_run_closed_loop_lanes, L = n_lanes > 1): one ring, shared by the
+ * lanes as the tracker and the pool cursor are -- the lanes loop runs its
+ * refills strictly in epoch order on the device (an epoch's wait for its
+ * predecessor, its execution, its refill, then its post).  The rule is
+ * dv_closed_loop_backoff's with one change: an abort of epoch k cannot return
+ * before epoch k + L.  Epochs are numbered as the tracker numbers them,
+ * D = n_slots.
+ *   After epoch k is decided, park: each aborted txn, in sequence order, with
+ *     a = its aborts + 1, is appended to slot (k + L - 1 + min(2^(a-1), D)) % D:
+ *     the a-th abort costs L - 1 + min(2^(a-1), D) epochs.  The delays still
+ *     fall into distinct slots.
+ *   Then build epoch e = k + L into that lane's other buffer: the first
+ *     R = min(c, n_txn) of the c entries of slot e % D open the epoch; the
+ *     other c - R (the spill) move, in order, to the tail of slot (e + 1) % D,
+ *     which the next refill releases, on the next lane; F = n_txn - R fresh
+ *     txns follow from the shared cursor.
+ *   Without resume the call's first L epochs are built by the same release
+ *     with no park before it, lane 0 first: an empty ring gives L all-fresh
+ *     epochs, as without a back-off.
+ *   D = 1 is the plain lanes loop bit for bit: epochs, commit bytes, cursor,
+ *     log, totals.  L = 1 is dv_closed_loop_backoff exactly (this entry with
+ *     n_lanes == 1 is that entry).
+ *   Unchanged: the capacity bound n_txn * (D + log2 D) entries a slot (the
+ *     aborts of epoch k fall due in k + L .. k + L - 1 + D), lost entries
+ *     (counted, not written, DV_ERR_ARG after the call's last epoch: one
+ *     8-byte read per call), the histogram's bins by abort count, counters[2]
+ *     summing (k - born) in loop epochs, counters[3] the ring's level.
+ * bo->aborts has 2 * n_lanes entries, indexed like the loop's bufs (lane l's
+ * pair at 2l, 2l + 1).  Requires a tracker with n_bufs == 2 * n_lanes attached
+ * to ctx (the loop's lanes[0]); detaching the tracker detaches the back-off;
+ * NULL detaches.  Refused at attach time: what dv_closed_loop_backoff refuses,
+ * n_lanes of 0 or above 8 (DV_ERR_ARG), a tracker whose n_bufs is not
+ * 2 * n_lanes (DV_ERR_STATE).
+ * The lanes loop accepts a back-off only on lanes[0], attached through this
+ * entry with the call's n_lanes: one attached through dv_closed_loop_backoff,
+ * or for another lane count, or to any other lane, is DV_ERR_STATE; so is an
+ * attachment with n_lanes > 1 at dv_epoch_run_closed_loop and
+ * dv_tpcc_epoch_run_closed_loop.  Each refusal comes before any launch and
+ * leaves cursor, tracker, ring and counters untouched.
+ * The refill chain is dv_closed_loop_backoff's, queued on the deciding lane
+ * behind its execution (reading that lane's statuses and counters), a no-op
+ * behind a halted or failed epoch; every later epoch is halted with it, and
+ * the host's redo parks and builds each epoch exactly once.  The ring, the
+ * counters, the wait partials and the lost count are lanes[0]'s; each lane
+ * brings the words one refill passes from kernel to kernel. */
+int dv_closed_loop_backoff_lanes(dv_ctx *ctx, const dv_loop_backoff *bo, uint32_t n_lanes);
 
 /* Epoch groups -- epoch-parallel scheduling for YCSB: a
  * group is P = nranks consecutive epochs of the sequencer, and homes[e]

@@ -11,7 +11,14 @@ commit, the mean (k - born) at commit, entries spilled per epoch, and the
 fullest the ring got.  The headline is committed txns/s against the plain
 loop's, same process, same box.  A last run per leg collects the per-launch
 kernel averages (DV_FLAG_KERNEL_PROFILE) of the refill's launches.  Prints
-one JSON line; `--out FILE` keeps it."""
+one JSON line; `--out FILE` keeps it.
+
+`--lanes L` (L > 1) measures the same legs on the closed loop over L decision
+lanes (dv_epoch_run_closed_loop_lanes under dv_closed_loop_backoff_lanes: one
+ring shared by the lanes, a txn's a-th abort costing L - 1 + min(2^(a-1), D)
+epochs) against the tracked plain lanes loop, whose every retry comes L
+epochs later; `--warmup` and `--epochs` are rounded up to multiples of 2 L
+(a resumed call continues each lane in its first buffer)."""
 import argparse
 import json
 import os
@@ -33,9 +40,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=40)
+    ap.add_argument("--lanes", type=int, default=1)
     ap.add_argument("--out")
     a = ap.parse_args()
-    n_txn = a.n_txn
+    n_txn, nl = a.n_txn, max(1, a.lanes)
+    if nl > 1:
+        a.warmup, a.epochs = (-(-v // (2 * nl)) * 2 * nl for v in (a.warmup, a.epochs))
     gen = dvcc.YCSBQueryGenerator(a.rows, part_cnt=1, req_per_query=10, zipf_theta=0.9, txn_write_perc=1.0,
                                   tup_write_perc=0.5, part_per_txn=1, strict_ppt=1, mpr=-1.0)
     pool = gen.gen(2 * n_txn, dvcc.epoch_seed(0, 999))
@@ -45,40 +55,48 @@ def main():
     eng = dvcc.CCEngine("NO_WAIT", n_txn, n_txn * 10)
     eng.set_stream(torch.cuda.current_stream().cuda_stream)
     eng.load_ycsb_partition(a.rows)
+    lanes = [eng.open_lane() for _ in range(nl - 1)]
     total = a.warmup + a.epochs
-    trk = dvcc.LoopTrack(n_txn, 2, log_cap=n_txn * total, epoch_cap=total, n_bins=64)
+    trk = dvcc.LoopTrack(n_txn, 2 * nl, log_cap=n_txn * total, epoch_cap=total, n_bins=64)
     rings = {D: dvcc.LoopBackoff(trk, D) for D in a.slots}
-    d_commit = torch.zeros(n_txn, dtype=torch.uint8, device="cuda")
+    # (the lanes decide epochs side by side: a commit array per epoch in flight)
+    d_commit = torch.zeros(n_txn, dtype=torch.uint8, device="cuda") if nl == 1 else \
+        [torch.zeros(n_txn, dtype=torch.uint8, device="cuda") for _ in range(2 * nl)]
     bufs = None
+
+    def loop(n, cursor, resume):
+        if nl == 1:
+            return eng.closed_loop(dpool, pb, n_txn, n, cursor=cursor, bufs=bufs, d_commits=d_commit, resume=resume,
+                                   track=trk)
+        return eng.closed_loop_lanes(lanes, dpool, pb, n_txn, n, cursor=cursor, bufs=bufs,
+                                     d_commits=[d_commit[k % (2 * nl)] for k in range(n)], resume=resume, track=trk)
 
     def run(D):
         """a fresh loop under back-off D (None: the tracked plain loop)"""
         nonlocal bufs
-        for t in (trk.log_pos, trk.epoch_end, trk.hist, trk.tot, trk.ids[0], trk.ids[1]):
+        for t in [trk.log_pos, trk.epoch_end, trk.hist, trk.tot] + trk.ids:
             t.zero_()
         trk.attach(eng)
         bo = rings.get(D)
         if bo is not None:
-            for t in (bo.slot_count, bo.ctr, bo.aborts[0], bo.aborts[1]):
+            for t in [bo.slot_count, bo.ctr] + bo.aborts:
                 t.zero_()
             bo.attach(eng)
 
-        def swap():
+        def swap():  # (one context only: the lanes' calls are multiples of 2 L epochs)
             bufs.swap()
             trk.swap()
             if bo is not None:
                 bo.swap()
 
         cursor = torch.zeros(1, dtype=torch.int32, device="cuda")
-        _, bufs, cursor = eng.closed_loop(dpool, pb, n_txn, a.warmup, cursor=cursor, bufs=bufs, d_commits=d_commit,
-                                          track=trk)
+        _, bufs, cursor = loop(a.warmup, cursor, False)
         if a.warmup & 1:
             swap()
         torch.cuda.synchronize()
         before = trk.totals() + (bo.counters() if bo is not None else [0, 0, 0, 0])
         t0 = time.perf_counter()
-        sts, bufs, cursor = eng.closed_loop(dpool, pb, n_txn, a.epochs, cursor=cursor, bufs=bufs, d_commits=d_commit,
-                                            resume=True, track=trk)
+        sts, bufs, cursor = loop(a.epochs, cursor, True)
         torch.cuda.synchronize()
         sec = time.perf_counter() - t0
         if a.epochs & 1:
@@ -91,7 +109,7 @@ def main():
             wait = after[6] - before[6]
             assert after[5] == 0, "entries lost: the ring's capacity bound does not hold"
             fullest = int(bo.slot_count.max().item())
-        else:  # (every retry one epoch later: k - born is the retry count; all epochs, warm-up included)
+        else:  # (every retry L epochs later: k - born is L times the retry count; all epochs, warm-up included)
             wait = None
             fullest = 0
         res = {"ms_per_epoch": round(sec / a.epochs * 1e3, 4), "committed_per_s": round(committed / sec, 1),
@@ -106,7 +124,7 @@ def main():
 
     legs = [None] + list(a.slots)
     name = lambda D: "plain" if D is None else f"D{D}"  # noqa: E731
-    out = {"rows": a.rows, "n_txn": n_txn, "warmup": a.warmup, "epochs": a.epochs, "rounds": a.rounds,
+    out = {"rows": a.rows, "n_txn": n_txn, "decision_lanes": nl, "warmup": a.warmup, "epochs": a.epochs, "rounds": a.rounds,
            "source": dvcc._lib.source_hash(), "legs": {name(D): [] for D in legs}}
     for _ in range(a.rounds):
         for D in legs:
