@@ -702,6 +702,24 @@ void launch_wire_plan(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf,
 void launch_wire_emit(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
                       uint32_t first, uint32_t nb, const dv_wire_dev_out &out, uint64_t next_txn,
                       const WireWs &ws);
+// the same two steps for TPC-C batches (dv_wire_ingest_device_tpcc): tp by
+// value into the kernels, cfg.tpcc never dereferenced on the device.  A batch
+// holds at most 20 messages (199 bytes each at least) and expands to fewer
+// than kWireTpccBatchAcc accesses: a message of n items is 199 + 24 n bytes at
+// least and 3 + 2 n accesses, 12 bytes an access at least, so a batch's 4,084
+// message bytes hold at most 340 of them.  kWireTpccMaxTxn + 1 batches -- what
+// a call looks at -- then keep every running sum of k_wire_scan / k_wire_plan
+// in 32 bits.
+constexpr uint32_t kWireTpccMaxTxn = 1u << 23;
+constexpr uint32_t kWireTpccBatchAcc = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / 12 + 1;
+static_assert(((uint64_t)kWireTpccMaxTxn + 1) * kWireTpccBatchAcc < (1ull << 32), "a call's accesses fit 32 bits");
+static_assert(((uint64_t)kWireTpccMaxTxn + 1) * kWireMaxMsg < (1ull << 32), "a call's txns fit 32 bits");
+void launch_wire_plan_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                           uint64_t buf_len, const uint64_t *off, uint32_t first, uint32_t nb, uint32_t n_batches,
+                           const dv_wire_tpcc_dev_out &out, uint64_t next_txn, const WireWs &ws);
+void launch_wire_emit_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                           const uint64_t *off, uint32_t first, uint32_t nb, const dv_wire_tpcc_dev_out &out,
+                           uint64_t next_txn, const WireWs &ws);
 // the committed txns' reply fields compacted in txn order; bc: reply_tiles(n_txn) + 1
 // words, bc[reply_tiles(n_txn)] = their count
 uint32_t reply_tiles(uint32_t n_txn);

@@ -3942,12 +3942,30 @@ int dv_tpcc_epoch_run(dv_ctx *c, const dv_access *acc, uint64_t n_acc, const uin
 }
 
 // ---- Deneva client batches decoded on the device (dvcc_wire.hip)
+// the context's per-call words for nb batches, its pinned result record and event
+static int wire_ws_prepare(dv_ctx *c, uint32_t nb) {
+    if (nb > c->wire_nb || !c->wire_ws) {  // (no captured graph names these words)
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dfree(c->wire_ws);
+        c->wire_ws = nullptr;
+        c->wire_nb = 0;
+        int r = dalloc(&c->wire_ws, wire_ws_bytes(nb));
+        if (r) return r;
+        c->wire_nb = nb ? nb : 1;
+    }
+    if (!c->wire_h) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
+    }
+    return DV_OK;
+}
+
 int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
                           const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
                           const dv_wire_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res) {
     KProfScope kps_(c);
     if (!c || !cfg || !buf || !off || !out || !res) return DV_ERR_ARG;
-    // TPC-C (dv_tpcc_expand, the last-name lists) and CALVIN (batch-id sequencing) stay on the host decoder
+    // TPC-C has its own entry (dv_wire_ingest_device_tpcc); CALVIN (batch-id sequencing) stays on the host decoder
     if (cfg->workload != DV_YCSB || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt) return DV_ERR_ARG;
     if (!out->txn_begin || !out->n_acc_dev || !out->max_txn || out->max_txn > kMaxTxn) return DV_ERR_ARG;
     const bool old_form = out->keys && out->types && out->acc_txn;
@@ -3962,19 +3980,8 @@ int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf,
     // and a stopper lies among the first max_txn + 1: the call looks no
     // further (and every sum of 40 txns / 170 accesses a batch stays in 32 bits).
     const uint32_t nb = std::min(n_batches - first_batch, out->max_txn + 1);
-    if (nb > c->wire_nb || !c->wire_ws) {  // (no captured graph names these words)
-        HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(c->wire_ws);
-        c->wire_ws = nullptr;
-        c->wire_nb = 0;
-        int r = dalloc(&c->wire_ws, wire_ws_bytes(nb));
-        if (r) return r;
-        c->wire_nb = nb ? nb : 1;
-    }
-    if (!c->wire_h) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
-    }
+    int r = wire_ws_prepare(c, nb);
+    if (r) return r;
     const WireWs ws = wire_ws_carve(c->wire_ws, c->wire_nb);
     launch_wire_plan(c->stream, *cfg, buf, buf_len, off, first_batch, nb, n_batches, *out, next_txn, ws);
     HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(dv_wire_dev_result), hipMemcpyDeviceToHost, c->stream));
@@ -3982,6 +3989,44 @@ int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf,
     launch_wire_emit(c->stream, *cfg, buf, off, first_batch, nb, *out, next_txn, ws);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone: the emit runs on
+    *res = *c->wire_h;
+    return res->status;
+}
+
+int dv_wire_ingest_device_tpcc(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                               const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
+                               const dv_wire_tpcc_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !buf || !off || !out || !res) return DV_ERR_ARG;
+    // CALVIN (batch-id sequencing) stays on the host decoder
+    if (cfg->workload != DV_TPCC || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt || !cfg->tpcc) return DV_ERR_ARG;
+    {  // the knobs dv_tpcc_expand accepts (its check of them, on no query)
+        uint64_t k, a;
+        uint8_t ty, tb;
+        uint32_t beg;
+        if (dv_tpcc_expand(cfg->tpcc, nullptr, 0, 0, &k, &ty, &tb, &a, &beg, nullptr, nullptr) != DV_OK)
+            return DV_ERR_ARG;
+    }
+    if (!out->txn_begin || !out->n_acc_dev || !out->keys || !out->types || !out->acc_txn || !out->tables || !out->args)
+        return DV_ERR_ARG;
+    if (!out->max_txn || out->max_txn > kWireTpccMaxTxn) return DV_ERR_ARG;
+    if (first_batch > n_batches) return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // As above, a stopper lies among the first max_txn + 1 batches; at most
+    // kWireTpccMaxTxn + 1 of them keep every sum of a batch's 20 txns and
+    // fewer than kWireTpccBatchAcc accesses in 32 bits.
+    const uint32_t nb = std::min(n_batches - first_batch, out->max_txn + 1);
+    int r = wire_ws_prepare(c, nb);
+    if (r) return r;
+    const dv_tpcc_params tp = *cfg->tpcc;
+    const WireWs ws = wire_ws_carve(c->wire_ws, c->wire_nb);
+    launch_wire_plan_tpcc(c->stream, *cfg, tp, buf, buf_len, off, first_batch, nb, n_batches, *out, next_txn, ws);
+    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(dv_wire_dev_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
+    launch_wire_emit_tpcc(c->stream, *cfg, tp, buf, off, first_batch, nb, *out, next_txn, ws);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone, as above
     *res = *c->wire_h;
     return res->status;
 }

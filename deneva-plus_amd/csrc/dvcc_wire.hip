@@ -14,7 +14,10 @@
 //   k_wire_plan    one workgroup: the chunks' prefixes, the first batch that
 //                  does not fit, the result record, the closing boundary
 //   k_wire_emit    the taken batches' boundaries, reply fields and accesses
-// and, for the replies, the committed txns' fields compacted in txn order
+// TPC-C CL_QRY batches (dv_wire_ingest_device_tpcc) take the same scan and
+// plan between k_wire_check_tpcc and k_wire_emit_tpcc, which expand every
+// message to its access list as dv_tpcc_expand does.
+// And, for the replies, the committed txns' fields compacted in txn order
 // (k_reply_count / k_reply_scan / k_reply_emit, like the carry-over's).
 // The byte stream has no alignment (COPY_BUF): fields are assembled from the
 // aligned words of the LDS image, never dereferenced in place.
@@ -357,6 +360,309 @@ void launch_wire_emit(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf,
                       const WireWs &ws) {
     if (!nb) return;
     DV_LAUNCH(k_wire_emit, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, off, first, out, next_txn, ws);
+}
+
+// ---- TPC-C client batches (dv_wire_ingest_device_tpcc): the same four
+// launches, k_wire_scan and k_wire_plan as they are.  A TPCCClientQueryMessage
+// is 199 + 8 np + 24 n bytes (kMsgFixed, the partitions, kTpccBody up to the
+// item count, the items, kTpccTail) and expands -- dv_tpcc_expand's lists, a
+// closed form of the message's fields per access -- to 3 accesses (Payment)
+// or 3 + 2 ol_cnt (NewOrder).  The knobs the lists follow come by value.
+namespace {
+
+constexpr uint32_t kTpccBody = 89;   // txn_type, w_id, d_id, c_id, d_w_id, c_w_id, c_d_id, c_last[16], h_amount,
+                                     // by_last_name, the item count
+constexpr uint32_t kTpccTail = 18;   // rbk, remote, ol_cnt, o_entry_d
+constexpr uint32_t kItemBytes = 24;  // sizeof(Item_no)
+constexpr uint32_t kTpccLast = 56, kTpccAmount = 72, kTpccByName = 80, kTpccN = 81;  // body offsets
+constexpr uint64_t kOperandMax = (1ull << 56) - 1;
+
+// 1 <= v <= bound, v the 64-bit field it is
+__device__ __forceinline__ bool in_1_to(uint64_t v, uint32_t bound) { return v - 1 < (uint64_t)bound; }
+// a zero byte somewhere in v
+__device__ __forceinline__ bool has_nul(uint64_t v) {
+    return ((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) != 0;
+}
+// custNPKey (tpcc_helper.cpp:35-43) of the name in c_last[16] (lo, hi: its
+// bytes, a NUL among them): the host's `char` arithmetic, a byte below 'A' or
+// at 0x80 and above sign-extended; the district's 10 bits overflow past
+// warehouse 102 (H8), kept
+__device__ __forceinline__ uint64_t cust_np_key(uint64_t lo, uint64_t hi, uint64_t dist) {
+    uint64_t key = 0;
+    bool open = true;
+#pragma unroll
+    for (uint32_t i = 0; i < 16; i++) {
+        const uint32_t ch = (uint32_t)((i < 8 ? lo >> (8 * i) : hi >> (8 * (i - 8))) & 0xFFu);
+        open = open && ch != 0;
+        if (open) key = (key << 1) + (uint64_t)(int64_t)((int32_t)(int8_t)ch - (int32_t)'A');
+    }
+    return (key << 10) + dist;
+}
+
+}  // namespace
+
+// dv_wire_open for a TPC-C cfg: read_client_part, read_tpcc, then
+// dv_tpcc_expand's checks.  Lane m checks message m's fixed fields; the
+// batch's NewOrder items are one flat range all lanes check.  Every count and
+// id is compared as the 64-bit value it is before it is multiplied or narrowed.
+__global__ __launch_bounds__(kBlock) void k_wire_check_tpcc(dv_wire_cfg cfg, dv_tpcc_params tp,
+                                                            const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                            const uint64_t *__restrict__ off, uint32_t first,
+                                                            uint32_t nb, WireWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint32_t s_it[kWireWave][64], s_pp[kWireWave][64];  // items to check / partitions before message m
+    __shared__ uint16_t s_mo[kWireWave][64], s_io[kWireWave][64];  // message m's offset, its first item's
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t b = blockIdx.x * kWireWave + wave;
+    const bool live = b < nb;
+    uint64_t o0 = 0;
+    uint32_t len = 0;
+    bool bad = live && !batch_span(off, first + b, buf_len, o0, len);
+    const bool parse = live && !bad;
+    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
+    if (parse) st.sh = stage_batch(buf + o0, len, s_img[wave], lane);
+    __syncthreads();
+    uint32_t count = 0, my_off = 0, my_np = 0, my_n = 0, my_bo = 0;
+    if (parse) {
+        count = st.u32(8);
+        bad = st.u32(0) != cfg.node_id || st.u32(4) == cfg.node_id || count == 0 || count > kWireMaxMsg;
+        uint32_t pos = DV_WIRE_HDR;
+        for (uint32_t m = 0; !bad && m < count; m++) {
+            if (pos + kMsgFixed > len) { bad = true; break; }
+            const uint64_t np = st.u64(pos + kMsgHdr + 8);
+            if (st.u32(pos) != DV_WIRE_CL_QRY || np > DV_TPCC_MAX_PARTS) { bad = true; break; }
+            const uint32_t bo = pos + kMsgFixed + (uint32_t)np * 8u;
+            if (bo + kTpccBody > len) { bad = true; break; }
+            const uint64_t n = st.u64(bo + kTpccN);
+            if (n > DV_TPCC_MAX_OL) { bad = true; break; }
+            const uint32_t end = bo + kTpccBody + (uint32_t)n * kItemBytes + kTpccTail;
+            if (end > len) { bad = true; break; }
+            if (lane == m) {
+                my_off = pos;
+                my_np = (uint32_t)np;
+                my_n = (uint32_t)n;
+                my_bo = bo;
+            }
+            pos = end;
+        }
+        if (!bad && pos != len) bad = true;  // exactly `count` messages fill exactly `len` bytes
+    }
+    // message m's fixed fields (a Payment's items are skipped unchecked)
+    bool wrong = false;
+    uint32_t my_acc = 0, my_it = 0;
+    if (parse && !bad && lane < count) {
+        const uint64_t tt = st.u64(my_bo), w = st.u64(my_bo + 8), d = st.u64(my_bo + 16), c = st.u64(my_bo + 24);
+        wrong = !in_1_to(w, tp.num_wh) || !in_1_to(d, tp.dist_per_wh);
+        if (tt == 1) {
+            wrong |= !in_1_to(st.u64(my_bo + 40), tp.num_wh) || !in_1_to(st.u64(my_bo + 48), tp.dist_per_wh) ||
+                     st.u64(my_bo + kTpccAmount) > kOperandMax;
+            if ((st.u32(my_bo + kTpccByName) & 0xFFu) != 0)
+                wrong |= !has_nul(st.u64(my_bo + kTpccLast)) && !has_nul(st.u64(my_bo + kTpccLast + 8));
+            else
+                wrong |= !in_1_to(c, tp.cust_per_dist);
+            my_acc = 3;
+        } else if (tt == 2) {
+            // the txn manager walks items[0 .. ol_cnt): the list must hold them, one at least
+            const uint64_t ol_cnt = st.u64(my_bo + kTpccBody + my_n * kItemBytes + 2);
+            wrong |= ol_cnt != my_n || my_n == 0 || !in_1_to(c, tp.cust_per_dist);
+            my_acc = 3 + 2 * my_n;
+            my_it = my_n;
+        } else {
+            wrong = true;
+        }
+    }
+    // (a bad batch's lanes hold zeros or a part of the chain: its tables are not read)
+    const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my_np, lane);
+    const uint32_t ac_in = wave_incl_sum(my_acc, lane);
+    const uint32_t tot_it = __shfl(it_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64), tot_ac = __shfl(ac_in, 63, 64);
+    uint32_t mx = my_acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t y = __shfl_xor(mx, o, 64);
+        mx = y > mx ? y : mx;
+    }
+    s_it[wave][lane] = it_in - my_it;
+    s_pp[wave][lane] = pp_in - my_np;
+    s_mo[wave][lane] = (uint16_t)my_off;
+    s_io[wave][lane] = (uint16_t)(my_bo + kTpccBody);
+    __syncthreads();
+    if (parse && !bad) {
+        for (uint32_t q = lane; q < tot_pp; q += 64) {  // every partition named below part_cnt
+            const uint32_t m = last_le64(s_pp[wave], q);
+            wrong |= st.u64(s_mo[wave][m] + kMsgFixed + (q - s_pp[wave][m]) * 8u) >= cfg.part_cnt;
+        }
+        for (uint32_t q = lane; q < tot_it; q += 64) {  // items inside the tables, operands of 56 bits
+            const uint32_t m = last_le64(s_it[wave], q);
+            const uint32_t io = s_io[wave][m] + (q - s_it[wave][m]) * kItemBytes;
+            wrong |= !in_1_to(st.u64(io), tp.max_items) || !in_1_to(st.u64(io + 8), tp.num_wh) ||
+                     st.u64(io + 16) > kOperandMax;
+        }
+    }
+    bad = bad || __any(wrong);
+    if (!live) return;
+    if (!bad && lane < count) ws.moff[(uint64_t)b * kWireMaxMsg + lane] = (uint16_t)my_off;
+    if (lane == 0) {
+        ws.bt[b] = bad ? 0u : count;
+        ws.ba[b] = bad ? 0u : tot_ac;
+        ws.bm[b] = bad ? (uint8_t)0 : (uint8_t)mx;  // (at most 3 + 2 * 62)
+        if (bad) atomicMin(ws.first_bad, b);
+    }
+}
+
+// the taken batches, a wave each: lane m message m's boundary, txn type, reply
+// fields and the keys of its three leading accesses; then all lanes the
+// batch's accesses in order -- consecutive lanes, consecutive accesses, access
+// r of message m from m's fields alone (dv_tpcc_expand's lists)
+__global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_tpcc_params tp,
+                                                           const uint8_t *__restrict__ buf,
+                                                           const uint64_t *__restrict__ off, uint32_t first,
+                                                           dv_wire_tpcc_dev_out out, uint64_t next_txn, WireWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint64_t s_hk[kWireWave][64][3], s_h[kWireWave][64];  // message m's leading keys, its h_amount
+    __shared__ uint32_t s_ac[kWireWave][64];                         // accesses before message m
+    __shared__ uint16_t s_io[kWireWave][64];                         // message m's first item
+    __shared__ uint32_t s_mt[kWireWave][64];  // Payment | by name << 1 | w_id's partition << 8 | c_w_id's << 16
+    const uint32_t taken = ws.res->n_taken - first;
+    if (blockIdx.x * kWireWave >= taken) return;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t b = blockIdx.x * kWireWave + wave;
+    const bool live = b < taken;  // (checked by k_wire_check_tpcc: its span and every field are good)
+    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
+    if (live) {
+        const uint64_t o0 = off[first + b];
+        st.sh = stage_batch(buf + o0, (uint32_t)(off[first + b + 1] - o0), s_img[wave], lane);
+    }
+    __syncthreads();
+    uint32_t count = 0, src = 0, my_acc = 0, my_io = 0, my_tt = 0, my_mt = 0, t0 = 0, a0 = 0;
+    uint64_t cst = 0, k0 = 0, k1 = 0, k2 = 0, h = 0;
+    if (live) {
+        src = st.u32(4);
+        count = st.u32(8);
+        t0 = ws.ct[b / kWireChunk] + ws.bt[b];
+        a0 = ws.ca[b / kWireChunk] + ws.ba[b];
+        if (lane < count) {
+            const uint32_t mo = ws.moff[(uint64_t)b * kWireMaxMsg + lane];
+            cst = st.u64(mo + kMsgHdr);
+            const uint32_t bo = mo + kMsgFixed + st.u32(mo + kMsgHdr + 8) * 8u;
+            my_io = bo + kTpccBody;
+            my_tt = st.u32(bo);
+            // (validated: every id below its 32-bit bound)
+            const uint32_t w = st.u32(bo + 8), d = st.u32(bo + 16), c = st.u32(bo + 24);
+            const uint64_t dist = (uint64_t)w * tp.dist_per_wh + d;
+            const uint32_t pw = (w - 1) % tp.part_cnt;  // wh_to_part
+            k0 = w;
+            if (my_tt == 1) {
+                const uint32_t c_w = st.u32(bo + 40), c_d = st.u32(bo + 48);
+                const uint64_t c_dist = (uint64_t)c_w * tp.dist_per_wh + c_d;
+                const bool by_name = (st.u32(bo + kTpccByName) & 0xFFu) != 0;
+                h = st.u64(bo + kTpccAmount);
+                k1 = dist;
+                k2 = by_name ? cust_np_key(st.u64(bo + kTpccLast), st.u64(bo + kTpccLast + 8), c_dist)
+                             : c_dist * tp.cust_per_dist + c;
+                my_mt = 1u | (by_name ? 2u : 0u) | ((pw & 0xFFu) << 8) | ((((c_w - 1) % tp.part_cnt) & 0xFFu) << 16);
+                my_acc = 3;
+            } else {
+                k1 = dist * tp.cust_per_dist + c;
+                k2 = dist;
+                my_mt = (pw & 0xFFu) << 8;
+                my_acc = 3 + 2 * st.u32(bo + kTpccN);
+            }
+        }
+    }
+    const uint32_t ac_in = wave_incl_sum(my_acc, lane);
+    const uint32_t tot_ac = __shfl(ac_in, 63, 64);
+    s_ac[wave][lane] = ac_in - my_acc;
+    s_io[wave][lane] = (uint16_t)my_io;
+    s_mt[wave][lane] = my_mt;
+    s_h[wave][lane] = h;
+    s_hk[wave][lane][0] = k0;
+    s_hk[wave][lane][1] = k1;
+    s_hk[wave][lane][2] = k2;
+    __syncthreads();
+    if (!live) return;
+    if (lane < count) {
+        const uint32_t t = t0 + lane;
+        out.txn_begin[t] = a0 + ac_in - my_acc;
+        if (out.txn_type) out.txn_type[t] = (uint8_t)my_tt;
+        // WorkerThread::get_next_txn_id for one worker (worker_thread.cpp:453-458)
+        if (out.txn_id) out.txn_id[t] = cfg.node_id + (uint64_t)cfg.node_cnt * (next_txn + t);
+        if (out.client_startts) out.client_startts[t] = cst;
+        if (out.return_node) out.return_node[t] = src;
+    }
+    for (uint32_t r = lane; r < tot_ac; r += 64) {
+        const uint32_t m = last_le64(s_ac[wave], r);
+        const uint32_t j = r - s_ac[wave][m], mt = s_mt[wave][m];
+        uint64_t key, arg;
+        uint32_t type, table, own = (mt >> 8) & 0xFFu;
+        if (j < 3) {
+            key = s_hk[wave][m][j];
+            if (mt & 1u) {  // run_payment_0..5: WAREHOUSE, DISTRICT, CUSTOMER (by id or through the name index)
+                const uint32_t op = j == 0 ? (tp.wh_update ? DV_TOP_PAY_WH : DV_TOP_NONE)
+                                           : (j == 1 ? DV_TOP_PAY_DIST : DV_TOP_PAY_CUST);
+                type = j == 0 && !tp.wh_update ? DV_RD : DV_WR;
+                table = j == 0 ? DV_TPCC_WAREHOUSE
+                               : (j == 1 ? DV_TPCC_DISTRICT : ((mt & 2u) ? DV_TPCC_CUST_LAST : DV_TPCC_CUSTOMER));
+                arg = (uint64_t)op << 56 | s_h[wave][m];
+                if (j == 2) own = (mt >> 16) & 0xFFu;
+            } else {  // new_order_0..5: WAREHOUSE RD, CUSTOMER RD, DISTRICT WR
+                type = j == 2 ? DV_WR : DV_RD;
+                table = j == 0 ? DV_TPCC_WAREHOUSE : (j == 1 ? DV_TPCC_CUSTOMER : DV_TPCC_DISTRICT);
+                arg = j == 2 ? (uint64_t)DV_TOP_NO_DIST << 56 : 0;
+            }
+        } else {  // new_order_6..9: ITEM RD, STOCK WR of item (j - 3) / 2, both with the supply warehouse
+            const uint32_t io = s_io[wave][m] + ((j - 3) >> 1) * kItemBytes;
+            const uint32_t i_id = st.u32(io), sw = st.u32(io + 8);
+            own = ((sw - 1) % tp.part_cnt) & 0xFFu;
+            if (j & 1u) {
+                key = i_id;
+                type = DV_RD;
+                table = DV_TPCC_ITEM;
+                arg = 0;
+            } else {
+                key = (uint64_t)sw * tp.max_items + i_id;
+                type = DV_WR;
+                table = DV_TPCC_STOCK;
+                arg = (uint64_t)DV_TOP_NO_STOCK << 56 | st.u64(io + 16);
+            }
+        }
+        const uint32_t a = a0 + r;
+        out.keys[a] = key;
+        out.types[a] = (uint8_t)type;
+        out.acc_txn[a] = t0 + m;
+        out.tables[a] = (uint8_t)table;
+        out.args[a] = arg;
+        if (out.owner) out.owner[a] = (uint8_t)own;
+    }
+}
+
+void launch_wire_plan_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                           uint64_t buf_len, const uint64_t *off, uint32_t first, uint32_t nb, uint32_t n_batches,
+                           const dv_wire_tpcc_dev_out &out, uint64_t next_txn, const WireWs &ws) {
+    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
+    dv_wire_cfg dc = cfg;
+    dc.tpcc = nullptr;  // (a host pointer: the kernels get the knobs by value)
+    dv_wire_dev_out pl{};  // what k_wire_plan reads of its out: the capacities, the boundaries, the count word
+    pl.max_txn = out.max_txn;
+    pl.max_acc = out.max_acc;
+    pl.txn_begin = out.txn_begin;
+    pl.n_acc_dev = out.n_acc_dev;
+    (void)hipMemsetAsync(ws.first_bad, 0xFF, sizeof(uint32_t), s);  // kNoBatch
+    if (nb) {
+        DV_LAUNCH(k_wire_check_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, dc, tp, buf, buf_len, off, first, nb,
+                  ws);
+        DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
+    }
+    DV_LAUNCH(k_wire_plan, 1, kBlock, 0, s, ws, first, nb, n_batches, nc, pl, next_txn);
+}
+
+void launch_wire_emit_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                           const uint64_t *off, uint32_t first, uint32_t nb, const dv_wire_tpcc_dev_out &out,
+                           uint64_t next_txn, const WireWs &ws) {
+    if (!nb) return;
+    dv_wire_cfg dc = cfg;
+    dc.tpcc = nullptr;
+    DV_LAUNCH(k_wire_emit_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, dc, tp, buf, off, first, out, next_txn,
+              ws);
 }
 
 // ---- the committed txns' reply fields, compacted in txn order

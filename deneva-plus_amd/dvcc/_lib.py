@@ -156,6 +156,14 @@ class WireDevOut(ctypes.Structure):  # dv_wire_dev_out: device output buffers of
                 ("return_node", ctypes.c_void_p)]
 
 
+class WireTpccDevOut(ctypes.Structure):  # dv_wire_tpcc_dev_out: those of dv_wire_ingest_device_tpcc
+    _fields_ = [("max_txn", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("max_acc", ctypes.c_uint64),
+                ("txn_begin", ctypes.c_void_p), ("n_acc_dev", ctypes.c_void_p), ("keys", ctypes.c_void_p),
+                ("types", ctypes.c_void_p), ("acc_txn", ctypes.c_void_p), ("tables", ctypes.c_void_p),
+                ("args", ctypes.c_void_p), ("txn_type", ctypes.c_void_p), ("owner", ctypes.c_void_p),
+                ("txn_id", ctypes.c_void_p), ("client_startts", ctypes.c_void_p), ("return_node", ctypes.c_void_p)]
+
+
 class WireDevResult(ctypes.Structure):  # dv_wire_dev_result
     _fields_ = [("status", ctypes.c_int32), ("n_taken", ctypes.c_uint32), ("n_txn", ctypes.c_uint32),
                 ("max_txn_acc", ctypes.c_uint32), ("n_acc", ctypes.c_uint64), ("next_txn", ctypes.c_uint64)]
@@ -275,6 +283,9 @@ SIGNATURES = [
                                        ctypes.c_uint32, _P(ctypes.c_uint32)]),
     ("dv_wire_ingest_device", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
                                              ctypes.c_uint32, _P(WireDevOut), ctypes.c_uint64, _P(WireDevResult)]),
+    ("dv_wire_ingest_device_tpcc", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                                  ctypes.c_uint32, _P(WireTpccDevOut), ctypes.c_uint64,
+                                                  _P(WireDevResult)]),
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),

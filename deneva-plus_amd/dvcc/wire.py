@@ -8,7 +8,9 @@ ended by RDONE -- decoded by libdvcc straight into the host arrays of an
 epoch, and the replies (CL_RSP to the clients, CALVIN_ACK to the sequencers)
 packed the same way from the epoch's commit bytes.  DeviceWireIngress does
 the YCSB ingress on the device instead (dv_wire_ingest_device): the receive
-queue's bytes in, a device-resident epoch out.
+queue's bytes in, a device-resident epoch out.  TpccDeviceWireIngress does the
+same for TPC-C client batches (dv_wire_ingest_device_tpcc), every message
+expanded to its access list on the device.
 """
 import ctypes
 from dataclasses import dataclass
@@ -153,7 +155,133 @@ class WireIngress:
         return [out[int(off[b]):int(off[b + 1])].tobytes() for b in range(nb.value)]
 
 
-class DeviceWireIngress:
+class _DeviceReplies:
+    """The replies of an epoch ingested on the device, whatever the workload:
+    what DeviceWireIngress and TpccDeviceWireIngress share (engine, cfg, _dev
+    and the three reply tensors txn_id / client_startts / return_node)."""
+
+    def respond(self, ep, d_commit):
+        """The CL_RSP batches (bytes) of the epoch's committed txns (d_commit:
+        device commit bytes): their reply fields compacted on the device, then
+        the host packer (dv_wire_respond) over them."""
+        import torch
+        n = ep.n_txn
+        tid = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
+        cst = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
+        rn = torch.empty(max(1, n), dtype=torch.int32, device=self._dev)
+        cnt = ctypes.c_uint32()
+        self.engine._after_torch()
+        L.check(L.lib().dv_wire_reply_fields_device(self.engine._ctx, d_commit.data_ptr(), n, ep.txn_id.data_ptr(),
+                                                    ep.client_startts.data_ptr(), ep.return_node.data_ptr(),
+                                                    tid.data_ptr(), cst.data_ptr(), rn.data_ptr(),
+                                                    ctypes.byref(cnt)), "dv_wire_reply_fields_device")
+        return self._pack(tid, cst, rn, cnt.value)
+
+    def _pack(self, tid, cst, rn, c):
+        """the host packer (dv_wire_respond) over the first c entries of device
+        reply fields, every one committed"""
+        if not c:
+            return []
+        e = L.WireEpoch()
+        e.n_txn, e.max_txn, e.batch_id = c, c, (1 << 64) - 1
+        h_tid, h_cst, h_rn = tid[:c].cpu().numpy(), cst[:c].cpu().numpy(), rn[:c].cpu().numpy()
+        e.txn_id, e.client_startts, e.return_node = h_tid.ctypes.data, h_cst.ctypes.data, h_rn.ctypes.data
+        cm = np.ones(max(1, c), np.uint8)
+        # (a batch holds (MSG_MAX - 12) // message size replies; one partial batch per destination)
+        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 7 * 8 + 8)
+        max_b = c // per + len(np.unique(h_rn)) + 1
+        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
+        off = np.zeros(max_b + 1, np.uint64)
+        nb = ctypes.c_uint32()
+        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
+                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
+        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
+
+    def respond_logged(self, src):
+        """The CL_RSP batches (bytes) of the pool txns `src` names: a slice of
+        a closed loop's commit log (LoopTrack.commits(i)[0], an integer device
+        tensor of indices into the epoch this ingress decoded last, which the
+        loop ran as its pool).  Their reply fields are gathered by index on the
+        device, then packed as respond packs its compacted ones -- a server
+        answering at commit, whatever epoch a txn committed in."""
+        import torch
+        idx = src.to(device=self.txn_id.device, dtype=torch.int64)
+        c = int(idx.numel())
+        if not c:
+            return []
+        self.engine._after_torch()
+        return self._pack(self.txn_id[idx], self.client_startts[idx], self.return_node[idx], c)
+
+    @staticmethod
+    def _upload(buf, off, device):
+        """numpy bytes / offsets as the device tensors the entry points take"""
+        import torch
+        if isinstance(buf, np.ndarray):
+            buf = torch.from_numpy(np.ascontiguousarray(buf, np.uint8)).to(device)
+        if isinstance(off, np.ndarray):
+            off = torch.from_numpy(np.ascontiguousarray(off, np.uint64).view(np.int64)).to(device)
+        return buf, off
+
+
+class TpccDeviceWireIngress(_DeviceReplies):
+    """dv_wire_ingest_device_tpcc over device buffers of max_txn txns and
+    max_acc accesses on `engine`'s context: a receive queue's TPC-C CL_QRY
+    batches into a DeviceEpoch with tables, whole batches at a time, the
+    access lists following `params` (dv_tpcc_params; the engine's own when it
+    is a TpccEngine running the epoch).  respond / respond_logged pack the
+    replies.  The epoch's tensors are the ingress's own: the next feed_buffer
+    overwrites them."""
+
+    def __init__(self, engine, params, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, device="cuda"):
+        import torch
+        self.engine = engine
+        self.params = params
+        self.cfg = L.WireCfg(L.TPCC, 0, node_id, node_cnt, part_cnt, 0, 0, ctypes.pointer(params))
+        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
+        self.next_txn = 0
+        A, T = max(1, self.max_acc), self.max_txn
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
+        self.txn_begin, self.n_acc_dev = new(T + 1, torch.int32), new(1, torch.int32)
+        self.keys, self.types, self.acc_txn = new(A, torch.int64), new(A, torch.uint8), new(A, torch.int32)
+        self.tables, self.args, self.owner = new(A, torch.uint8), new(A, torch.int64), new(A, torch.uint8)
+        self.txn_type = new(T, torch.uint8)
+        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
+        self.return_node = new(T, torch.int32)
+        self._dev = device
+
+    def feed_buffer(self, buf, off, first_batch=0):
+        """Batches first_batch.. of buf (a torch uint8 device tensor, or a numpy
+        array, uploaded) at offsets off (u64 [n + 1], numpy or an int64 device
+        tensor) -> (epoch, n_taken, status), status as DeviceWireIngress's.
+        The epoch (DeviceEpoch with tables, of exact size) is written on the
+        engine's stream and carries args (its operation words), txn_begin,
+        txn_type, owner and the device reply arrays: run it with
+        run_tpcc_epoch_device(ep, ep.args, ...), or hand it to closed_loop as
+        the pool (ep, ep.args, ep.txn_begin)."""
+        buf, off = self._upload(buf, off, self._dev)
+        self.engine._after_torch()
+        p = lambda t: t.data_ptr()  # noqa: E731
+        out = L.WireTpccDevOut(self.max_txn, 0, self.max_acc, p(self.txn_begin), p(self.n_acc_dev), p(self.keys),
+                               p(self.types), p(self.acc_txn), p(self.tables), p(self.args), p(self.txn_type),
+                               p(self.owner), p(self.txn_id), p(self.client_startts), p(self.return_node))
+        res = L.WireDevResult()
+        rc = L.lib().dv_wire_ingest_device_tpcc(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(), buf.numel(),
+                                                off.data_ptr(), off.numel() - 1, first_batch, ctypes.byref(out),
+                                                self.next_txn, ctypes.byref(res))
+        if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or (rc == L.DV_ERR_ARG and res.status != rc):
+            L.check(rc, "dv_wire_ingest_device_tpcc")  # (refused before any launch, or a HIP failure)
+        self._held = (buf, off)  # (the decode may still read them when this returns)
+        self.next_txn = res.next_txn
+        n, a = res.n_txn, res.n_acc
+        ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n, tables=self.tables[:a],
+                                      max_txn_acc=res.max_txn_acc)
+        ep.args, ep.owner = self.args[:a], self.owner[:a]
+        ep.txn_begin, ep.txn_type = self.txn_begin[:n + 1], self.txn_type[:n]
+        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
+        return ep, res.n_taken, res.status
+
+
+class DeviceWireIngress(_DeviceReplies):
     """dv_wire_ingest_device / dv_wire_reply_fields_device over device
     buffers of max_txn txns and max_acc accesses on `engine`'s context (YCSB,
     NO_WAIT / WAIT_DIE / OCC).  feed_buffer decodes a receive queue's batches
@@ -209,11 +337,7 @@ class DeviceWireIngress:
         capacity); the epoch holds the batches before it.  The epoch is
         written on the engine's stream (run it there; other streams
         synchronise first) and carries the device reply arrays."""
-        import torch
-        if isinstance(buf, np.ndarray):
-            buf = torch.from_numpy(np.ascontiguousarray(buf, np.uint8)).to(self._dev)
-        if isinstance(off, np.ndarray):
-            off = torch.from_numpy(np.ascontiguousarray(off, np.uint64).view(np.int64)).to(self._dev)
+        buf, off = self._upload(buf, off, self._dev)
         self.engine._after_torch()
         # records and boundaries alone when the epoch takes the tb-mode prefix
         # path, both forms otherwise -- as loop_form picks for the closed loop.
@@ -239,58 +363,6 @@ class DeviceWireIngress:
                                           max_txn_acc=res.max_txn_acc)
         ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
         return ep, res.n_taken, res.status
-
-    def respond(self, ep, d_commit):
-        """The CL_RSP batches (bytes) of the epoch's committed txns (d_commit:
-        device commit bytes): their reply fields compacted on the device, then
-        the host packer (dv_wire_respond) over them."""
-        import torch
-        n = ep.n_txn
-        tid = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
-        cst = torch.empty(max(1, n), dtype=torch.int64, device=self._dev)
-        rn = torch.empty(max(1, n), dtype=torch.int32, device=self._dev)
-        cnt = ctypes.c_uint32()
-        self.engine._after_torch()
-        L.check(L.lib().dv_wire_reply_fields_device(self.engine._ctx, d_commit.data_ptr(), n, ep.txn_id.data_ptr(),
-                                                    ep.client_startts.data_ptr(), ep.return_node.data_ptr(),
-                                                    tid.data_ptr(), cst.data_ptr(), rn.data_ptr(),
-                                                    ctypes.byref(cnt)), "dv_wire_reply_fields_device")
-        return self._pack(tid, cst, rn, cnt.value)
-
-    def _pack(self, tid, cst, rn, c):
-        """the host packer (dv_wire_respond) over the first c entries of device
-        reply fields, every one committed"""
-        if not c:
-            return []
-        e = L.WireEpoch()
-        e.n_txn, e.max_txn, e.batch_id = c, c, (1 << 64) - 1
-        h_tid, h_cst, h_rn = tid[:c].cpu().numpy(), cst[:c].cpu().numpy(), rn[:c].cpu().numpy()
-        e.txn_id, e.client_startts, e.return_node = h_tid.ctypes.data, h_cst.ctypes.data, h_rn.ctypes.data
-        cm = np.ones(max(1, c), np.uint8)
-        # (a batch holds (MSG_MAX - 12) // message size replies; one partial batch per destination)
-        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 7 * 8 + 8)
-        max_b = c // per + len(np.unique(h_rn)) + 1
-        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
-        off = np.zeros(max_b + 1, np.uint64)
-        nb = ctypes.c_uint32()
-        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
-                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
-        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
-
-    def respond_logged(self, src):
-        """The CL_RSP batches (bytes) of the pool txns `src` names: a slice of
-        a closed loop's commit log (LoopTrack.commits(i)[0], an integer device
-        tensor of indices into the epoch this ingress decoded last, which the
-        loop ran as its pool).  Their reply fields are gathered by index on the
-        device, then packed as respond packs its compacted ones -- a server
-        answering at commit, whatever epoch a txn committed in."""
-        import torch
-        idx = src.to(device=self.txn_id.device, dtype=torch.int64)
-        c = int(idx.numel())
-        if not c:
-            return []
-        self.engine._after_torch()
-        return self._pack(self.txn_id[idx], self.client_startts[idx], self.return_node[idx], c)
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

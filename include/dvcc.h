@@ -59,9 +59,9 @@
  *   dv_wire_respond             CL_RSP / CALVIN_ACK replies (worker_thread.cpp:127-152;
  *                               message.cpp:921-949, 1057-1110) packed as MessageThread does
  *                               (transport/msg_thread.cpp:53-111)
- *   dv_wire_ingest_device /     the same receive path for YCSB client batches already in
- *   dv_wire_reply_fields_device device memory, into a device epoch; the committed txns'
- *                               reply fields compacted for dv_wire_respond
+ *   dv_wire_ingest_device /     the same receive path for YCSB / TPC-C client batches
+ *   dv_wire_ingest_device_tpcc /  already in device memory, into a device epoch; the
+ *   dv_wire_reply_fields_device committed txns' reply fields compacted for dv_wire_respond
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
  * the final table state equal a single worker thread running the same epoch
@@ -1126,9 +1126,10 @@ int dv_wire_respond(const dv_wire_cfg *cfg, const dv_wire_epoch *ep, const uint8
                     uint64_t cap, uint64_t *batch_off, uint32_t max_batches, uint32_t *n_batches);
 
 /* ---- the same ingress on the device (dvcc_wire.hip): a receive queue's bytes
- * as they are, in device memory, into a device-resident epoch.  YCSB without
- * CALVIN only (TPC-C needs dv_tpcc_expand and the last-name lists on the
- * host, CALVIN its batch-id sequencing: DV_ERR_ARG, use the host decoder).
+ * as they are, in device memory, into a device-resident epoch.  Without
+ * CALVIN only (its batch-id sequencing stays on the host decoder: DV_ERR_ARG).
+ * dv_wire_ingest_device takes YCSB batches and refuses TPC-C, which has an
+ * entry of its own below (dv_wire_ingest_device_tpcc).
  * The caller's device output buffers and their capacities: */
 typedef struct dv_wire_dev_out {
     uint32_t max_txn, pad_;      /* 1 .. 2^24                                              */
@@ -1180,6 +1181,57 @@ typedef struct dv_wire_dev_result {
 int dv_wire_ingest_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
                           const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
                           const dv_wire_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res);
+
+/* ---- TPC-C client batches on the device.  A TPCCClientQueryMessage's access
+ * list (dv_tpcc_expand) is arithmetic on the message's fields and
+ * dv_tpcc_params alone: a Payment by last name becomes a DV_TPCC_CUST_LAST
+ * access keyed custNPKey(c_last, c_d_id, c_w_id), which the engine's probe
+ * resolves against the name index on the device -- nothing of the expansion
+ * needs host state.  The caller's device output buffers: */
+typedef struct dv_wire_tpcc_dev_out {
+    uint32_t max_txn, pad_;      /* 1 .. 2^23 (see below)                                  */
+    uint64_t max_acc;
+    uint32_t *txn_begin;         /* [max_txn + 1]                                          */
+    uint32_t *n_acc_dev;         /* one word: the epoch's access count                     */
+    uint64_t *keys;              /* [max_acc]                                              */
+    uint8_t *types;              /* [max_acc] DV_RD / DV_WR                                */
+    uint32_t *acc_txn;           /* [max_acc] the txn whose range holds the access         */
+    uint8_t *tables;             /* [max_acc] DV_TPCC_*                                    */
+    uint64_t *args;              /* [max_acc] op << 56 | operand                           */
+    uint8_t *txn_type;           /* [max_txn] optional: 1 Payment, 2 NewOrder              */
+    uint8_t *owner;              /* [max_acc] optional: wh_to_part of the access's warehouse */
+    uint64_t *txn_id;            /* [max_txn] optional                                     */
+    uint64_t *client_startts;    /* [max_txn] optional                                     */
+    uint32_t *return_node;       /* [max_txn] optional: the batch's src                    */
+} dv_wire_tpcc_dev_out;
+
+/* dv_wire_ingest_device for TPC-C CL_QRY batches, with the same meaning of
+ * every argument, of DV_OK / DV_WIRE_MORE / DV_ERR_ARG and of *res: whole
+ * batches taken in order up to the first stopper in batch order (all taken;
+ * the next batch's txns or accesses do not fit max_txn / max_acc; the next
+ * batch is malformed -- whatever dv_wire_open refuses under a DV_TPCC cfg, or
+ * a bad off), nothing written at or past txn n_txn (txn_begin: n_txn + 1) or
+ * access n_acc, queued on the context's stream, waiting for the result record
+ * alone.  For the taken batches keys, types, tables, args, txn_begin,
+ * txn_type, owner, txn_id, client_startts and return_node equal what
+ * dv_wire_decode_batches writes with the same cfg, bit for bit; acc_txn[a] is
+ * the txn whose range holds a.  The context supplies the stream and the
+ * per-call words only: the access lists follow cfg->tpcc (read on the host,
+ * passed to the kernels by value), whatever tables the context holds.
+ * max_txn <= 2^23: a call looks at max_txn + 1 batches at most, and a message
+ * of n items is 199 + 24 n bytes at least for 3 + 2 n accesses at most -- 12
+ * bytes an access at least, so the 4,084 message bytes of a batch expand to
+ * at most 340 accesses (two 62-item NewOrders and a 21-item one: 299) in at
+ * most 20 txns; (2^23 + 1) x 341 < 2^32 keeps every running sum of the
+ * batches' counts in 32 bits, which 2^24 batches would not.
+ * Refused before any launch (DV_ERR_ARG, *res untouched): a null pointer, a
+ * workload other than DV_TPCC, CALVIN, a null cfg->tpcc or knobs
+ * dv_tpcc_expand refuses, a missing required array (all but the last five),
+ * zero part_cnt / node_cnt, first_batch > n_batches, max_txn outside
+ * 1 .. 2^23. */
+int dv_wire_ingest_device_tpcc(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                               const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
+                               const dv_wire_tpcc_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res);
 /* The reply fields of the committed txns (commit[t] != 0, device bytes) of an
  * epoch ingested on the device: txn_id / client_startts / return_node
  * (device, [n_txn]) compacted in txn order into out_* (device or host-mapped,
