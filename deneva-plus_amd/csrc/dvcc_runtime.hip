@@ -185,6 +185,8 @@ struct dv_ctx {
     // and the pinned words the two entries read back (the result record, the count)
     uint8_t *wire_ws = nullptr;
     uint32_t wire_nb = 0;
+    uint8_t *wire_cws = nullptr;                     // dv_wire_ingest_device_calvin's words of wire_cnb mbufs
+    uint32_t wire_cnb = 0;
     uint32_t *reply_bc = nullptr;
     uint32_t reply_nt = 0;
     dv_wire_dev_result *wire_h = nullptr;
@@ -737,7 +739,7 @@ void dv_close(dv_ctx *c) {
                     c->d_tables, c->d_commit, c->d_txn, c->d_grant, c->d_tb, c->split_err,
                     c->d_args, c->d_oid, c->tp_dsnap,
                     c->row_state, c->b_status, c->b_tlen, c->b_map, c->kinfo, c->ktsum, c->kill_bits, c->gc_tb, c->gc_tot,
-                    c->wire_ws, c->reply_bc,
+                    c->wire_ws, c->wire_cws, c->reply_bc,
                     c->hslot[0].acc, c->hslot[0].tb, c->hslot[1].acc, c->hslot[1].tb};
     for (void *b : bufs) dfree(b);
     for (auto &h : c->hslot) {
@@ -4029,6 +4031,51 @@ int dv_wire_ingest_device_tpcc(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t 
     HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone, as above
     *res = *c->wire_h;
     return res->status;
+}
+
+int dv_wire_ingest_device_calvin(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                                 const uint64_t *off, uint32_t n_batches, const dv_wire_dev_out *out,
+                                 dv_wire_calvin_pos *pos) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !buf || !off || !out || !pos) return DV_ERR_ARG;
+    // (TPC-C under CALVIN stays on the host decoder)
+    if (cfg->workload != DV_YCSB || !cfg->calvin || !cfg->part_cnt || !cfg->node_cnt) return DV_ERR_ARG;
+    if (!out->txn_begin || !out->keys || !out->types || !out->acc_txn) return DV_ERR_ARG;
+    if (out->recs32 && cfg->synth_table_size > (1ull << 31)) return DV_ERR_ARG;
+    if (!out->max_txn || out->max_txn > kMaxTxn || out->max_acc >= (1ull << 32)) return DV_ERR_ARG;
+    if (pos->batch > n_batches || (pos->batch == n_batches && pos->msg != 0)) return DV_ERR_ARG;
+    if (pos->n_txn > out->max_txn || pos->n_acc > out->max_acc) return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // A taken mbuf that is not RDONEs alone holds a txn, so among the first
+    // (max_txn - n_txn) + 1 such mbufs lies a stopper; RDONE-only mbufs may
+    // stretch that, and the window then ends the call (DV_WIRE_STOP_WINDOW).
+    // At most kMaxTxn + 1 mbufs keep every running sum in 32 bits.
+    const uint32_t window = std::max(out->max_txn - pos->n_txn + 1, 256u);
+    const uint32_t nb = std::min(n_batches - pos->batch, window);
+    if (nb > c->wire_cnb || !c->wire_cws) {  // (no captured graph names these words)
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dfree(c->wire_cws);
+        c->wire_cws = nullptr;
+        c->wire_cnb = 0;
+        int r = dalloc(&c->wire_cws, wire_calvin_ws_bytes(nb));
+        if (r) return r;
+        c->wire_cnb = nb ? nb : 1;
+    }
+    if (!c->wire_h) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
+    }
+    const WireCalvinWs ws = wire_calvin_ws_carve(c->wire_cws, c->wire_cnb);
+    launch_wire_plan_calvin(c->stream, *cfg, buf, buf_len, off, nb, n_batches, *out, *pos, ws);
+    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(WireCalvinRes), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
+    launch_wire_emit_calvin(c->stream, *cfg, buf, off, nb, *out, *pos, ws);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone, as above
+    const WireCalvinRes *h = reinterpret_cast<const WireCalvinRes *>(c->wire_h);
+    *pos = h->pos;
+    return h->status;
 }
 
 int dv_wire_reply_fields_device(dv_ctx *c, const uint8_t *commit, uint32_t n_txn, const uint64_t *txn_id,

@@ -17,6 +17,9 @@
 // TPC-C CL_QRY batches (dv_wire_ingest_device_tpcc) take the same scan and
 // plan between k_wire_check_tpcc and k_wire_emit_tpcc, which expand every
 // message to its access list as dv_tpcc_expand does.
+// CALVIN sequencer streams (dv_wire_ingest_device_calvin, YCSB) have the four
+// launches as kernels of their own, k_wire_*_calvin: the header carries
+// batch_id, RDONE ends a batch, and the epoch is cut at a message.
 // And, for the replies, the committed txns' fields compacted in txn order
 // (k_reply_count / k_reply_scan / k_reply_emit, like the carry-over's).
 // The byte stream has no alignment (COPY_BUF): fields are assembled from the
@@ -663,6 +666,403 @@ void launch_wire_emit_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_
     dc.tpcc = nullptr;
     DV_LAUNCH(k_wire_emit_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, dc, tp, buf, off, first, out, next_txn,
               ws);
+}
+
+// ---- CALVIN sequencer streams (dv_wire_ingest_device_calvin): the same four
+// launches with kernels of their own.  The header carries batch_id (84 bytes),
+// an RDONE is the header alone, and the stream is cut at a message: an mbuf's
+// run is its messages from the cursor that name the epoch's batch E, and an
+// epoch ends inside the first mbuf whose run does not reach its end.  The
+// check cannot know E (it may be the first mbuf's own), so it measures every
+// mbuf's run against the id of its own first message; the scan, which knows
+// E, drops the mbufs that lead with another id and finds the first cut.
+namespace {
+
+constexpr uint32_t kCalHdr = 84;     // rtype, txn_id, batch_id, mq_time, 7 latencies (Message::mget_size, CALVIN)
+constexpr uint32_t kCalFixed = 100;  // ... client_startts, the partition count
+constexpr uint32_t kCalTxnId = 4, kCalBatchId = 12;  // header offsets
+constexpr uint64_t kNoBatchId = ~0ull;
+constexpr uint32_t kRunLater = 1, kRunEarlier = 2;  // WireCalvinWs::bflag
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {
+    return ((uint64_t)__shfl((uint32_t)(v >> 32), (int)src, 64) << 32) | __shfl((uint32_t)v, (int)src, 64);
+}
+
+}  // namespace
+
+// Whatever dv_wire_open refuses under a CALVIN cfg makes the mbuf bad, whole
+// (every length compared as the 64-bit count it is, as k_wire_check does), and
+// so does a cursor at or past its count.  Lane m keeps message m's rtype and
+// batch id: the run is the lanes from the cursor up to the first whose id
+// differs from the cursor's.
+__global__ __launch_bounds__(kBlock) void k_wire_check_calvin(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
+                                                              uint64_t buf_len, const uint64_t *__restrict__ off,
+                                                              uint32_t first, uint32_t msg0, uint32_t nb,
+                                                              WireCalvinWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint32_t s_rq[kWireWave][64], s_pp[kWireWave][64];  // requests / partitions before message m
+    __shared__ uint16_t s_mo[kWireWave][64], s_p2[kWireWave][64];  // message m's offset, its request count's
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t b = blockIdx.x * kWireWave + wave;
+    const bool live = b < nb;
+    uint64_t o0 = 0;
+    uint32_t len = 0;
+    bool bad = live && !batch_span(off, first + b, buf_len, o0, len);
+    const bool parse = live && !bad;
+    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
+    if (parse) st.sh = stage_batch(buf + o0, len, s_img[wave], lane);
+    __syncthreads();
+    const uint32_t m0 = b == 0 ? msg0 : 0;  // the cursor's message (the window's first mbuf is the cursor's)
+    uint32_t count = 0, my_off = 0, my_np = 0, my_n = 0, my_p2 = 0, my_rt = 0;
+    uint64_t my_bid = 0;
+    if (parse) {
+        count = st.u32(8);
+        bad = st.u32(0) != cfg.node_id || st.u32(4) == cfg.node_id || count == 0 || count > kWireCalvinMaxMsg ||
+              m0 >= count;
+        const uint32_t lim = cfg.max_req && cfg.max_req < kReqMax ? cfg.max_req : kReqMax;
+        uint32_t pos = DV_WIRE_HDR;
+        for (uint32_t m = 0; !bad && m < count; m++) {
+            if (pos + kCalHdr > len) { bad = true; break; }
+            const uint32_t rt = st.u32(pos);
+            const uint64_t bid = st.u64(pos + kCalBatchId);
+            if (bid == kNoBatchId) { bad = true; break; }
+            uint32_t end = pos + kCalHdr, np32 = 0, n32 = 0, p2 = 0;
+            if (rt == DV_WIRE_CL_QRY) {
+                if (pos + kCalFixed > len) { bad = true; break; }
+                const uint64_t np = st.u64(pos + kCalHdr + 8);
+                if (np > DV_TPCC_MAX_PARTS) { bad = true; break; }
+                p2 = pos + kCalFixed + (uint32_t)np * 8u;
+                if (p2 + 8 > len) { bad = true; break; }
+                const uint64_t n = st.u64(p2);
+                if (n > lim) { bad = true; break; }
+                end = p2 + 8 + (uint32_t)n * kReqBytes;
+                if (end > len) { bad = true; break; }
+                np32 = (uint32_t)np;
+                n32 = (uint32_t)n;
+            } else if (rt != DV_WIRE_RDONE) {
+                bad = true;
+                break;
+            }
+            if (lane == m) {
+                my_off = pos;
+                my_np = np32;
+                my_n = n32;
+                my_p2 = p2;
+                my_rt = rt;
+                my_bid = bid;
+            }
+            pos = end;
+        }
+        if (!bad && pos != len) bad = true;  // exactly `count` messages fill exactly `len` bytes
+    }
+    // (a bad mbuf's lanes hold zeros or a part of the chain: its tables are not read)
+    const uint32_t rq_in = wave_incl_sum(my_n, lane), pp_in = wave_incl_sum(my_np, lane);
+    const uint32_t tot_rq = __shfl(rq_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64);
+    s_rq[wave][lane] = rq_in - my_n;
+    s_pp[wave][lane] = pp_in - my_np;
+    s_mo[wave][lane] = (uint16_t)my_off;
+    s_p2[wave][lane] = (uint16_t)my_p2;
+    __syncthreads();
+    bool wrong = false;
+    if (parse && !bad) {  // every message of the mbuf, in the run or not: it is refused whole
+        for (uint32_t q = lane; q < tot_pp; q += 64) {  // every partition named below part_cnt
+            const uint32_t m = last_le64(s_pp[wave], q);
+            wrong |= st.u64(s_mo[wave][m] + kCalFixed + (q - s_pp[wave][m]) * 8u) >= cfg.part_cnt;
+        }
+        for (uint32_t r = lane; r < tot_rq; r += 64) {  // RD / WR of keys inside the table
+            const uint32_t m = last_le64(s_rq[wave], r);
+            const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
+            wrong |= st.u32(ro) > DV_WR || st.u64(ro + 8) >= cfg.synth_table_size;
+        }
+    }
+    bad = bad || __any(wrong);
+    // the run: lanes [m0, rend), the first lane behind the cursor whose id is not the cursor's
+    const uint64_t lead = shfl_u64(my_bid, m0 & 63u);
+    const uint64_t differ = __ballot(lane >= m0 && lane < count && my_bid != lead);
+    const uint32_t rend = differ ? (uint32_t)__ffsll((long long)differ) - 1u : count;
+    const bool in_run = lane >= m0 && lane < rend;
+    const bool is_q = in_run && my_rt == DV_WIRE_CL_QRY;
+    const uint32_t txns = (uint32_t)__popcll(__ballot(is_q));
+    const uint32_t rdones = (uint32_t)__popcll(__ballot(in_run && my_rt == DV_WIRE_RDONE));
+    const uint32_t run_n = is_q ? my_n : 0u;
+    const uint32_t accs = __shfl(wave_incl_sum(run_n, lane), 63, 64);
+    uint32_t mx = run_n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t y = __shfl_xor(mx, o, 64);
+        mx = y > mx ? y : mx;
+    }
+    const uint64_t behind = shfl_u64(my_bid, rend & 63u);
+    if (!live) return;
+    if (!bad && lane < count) ws.moff[(uint64_t)b * kWireCalvinMaxMsg + lane] = (uint16_t)my_off;
+    if (lane == 0) {
+        ws.bt[b] = bad ? 0u : txns;
+        ws.ba[b] = bad ? 0u : accs;
+        ws.br[b] = bad ? 0u : rdones;
+        ws.bm[b] = bad ? (uint8_t)0 : (uint8_t)mx;
+        ws.bid[b] = bad ? kNoBatchId : lead;
+        ws.brun[b] = bad ? (uint8_t)0 : (uint8_t)(rend - m0);
+        ws.bflag[b] = bad || rend >= count ? (uint8_t)0 : (uint8_t)(behind > lead ? kRunLater : kRunEarlier);
+        if (bad) atomicMin(&ws.first[0], b);
+    }
+}
+
+// chunk blockIdx.x: an mbuf that leads with another id than E has an empty run
+// (its counts go); the first such mbuf, or the first whose run ends inside it,
+// is where the batch ends; then the counts become prefixes inside the chunk.
+// E by value, or -- none yet -- the id the check read at the cursor.
+__global__ __launch_bounds__(kBlock) void k_wire_scan_calvin(WireCalvinWs ws, uint32_t nb, uint64_t batch_id) {
+    __shared__ uint32_t lds4[4], s_max;
+    const uint64_t E = batch_id != kNoBatchId ? batch_id : ws.bid[0];
+    const uint32_t base = blockIdx.x * kWireChunk;
+    const uint32_t n = nb - base < kWireChunk ? nb - base : kWireChunk;
+    if (threadIdx.x == 0) s_max = 0;
+    uint32_t mx = 0, cut = kNoBatch;
+    for (uint32_t j = threadIdx.x; j < n; j += kBlock) {
+        const uint32_t g = base + j;
+        if (ws.bid[g] != E) {
+            ws.bt[g] = ws.ba[g] = ws.br[g] = 0;
+            ws.bm[g] = 0;
+            cut = g < cut ? g : cut;
+        } else {
+            if (ws.bflag[g]) cut = g < cut ? g : cut;
+            mx = ws.bm[g] > mx ? ws.bm[g] : mx;
+        }
+    }
+    if (cut != kNoBatch) atomicMin(&ws.first[1], cut);
+    __syncthreads();  // (the counts dropped above are read by other threads below)
+    atomicMax(&s_max, mx);
+    const uint32_t t = block_chunk_scan256(ws.bt + base, n, lds4);
+    const uint32_t a = block_chunk_scan256(ws.ba + base, n, lds4);
+    const uint32_t r = block_chunk_scan256(ws.br + base, n, lds4);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws.ct[blockIdx.x] = t;
+        ws.ca[blockIdx.x] = a;
+        ws.cr[blockIdx.x] = r;
+        ws.cm[blockIdx.x] = s_max;
+    }
+}
+
+// One workgroup.  Mbuf by mbuf the first stopper decides, and inside an mbuf a
+// malformed one comes before its capacity test, which comes before the end of
+// its run: the minimum of the first bad mbuf, the first whose run, added to
+// the epoch's and the runs' before it, passes the capacities (the running sums
+// only grow; past the batch's end they count mbufs never reached, and the
+// minimum ignores them) and the first where the batch ends.
+__global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, uint32_t nb, uint32_t n_batches,
+                                                             uint32_t nc, dv_wire_dev_out out,
+                                                             dv_wire_calvin_pos pos) {
+    __shared__ uint32_t lds4[4], s_chunk, s_cut, s_max;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        s_chunk = nc;
+        s_cut = nb;
+        s_max = 0;
+    }
+    const uint32_t tot_t = block_chunk_scan256(ws.ct, nc, lds4);
+    const uint32_t tot_a = block_chunk_scan256(ws.ca, nc, lds4);
+    const uint32_t tot_r = block_chunk_scan256(ws.cr, nc, lds4);
+    __syncthreads();
+    const uint64_t room_t = out.max_txn - pos.n_txn, room_a = out.max_acc - pos.n_acc;  // (checked: not negative)
+    for (uint32_t i = tid; i < nc; i += kBlock) {
+        const uint32_t it = i + 1 < nc ? ws.ct[i + 1] : tot_t, ia = i + 1 < nc ? ws.ca[i + 1] : tot_a;
+        if (it > room_t || ia > room_a) atomicMin(&s_chunk, i);
+    }
+    __syncthreads();
+    const uint32_t cc = s_chunk;
+    if (cc < nc) {
+        const uint32_t base = cc * kWireChunk;
+        const uint32_t n = nb - base < kWireChunk ? nb - base : kWireChunk;
+        const uint32_t t0 = ws.ct[cc], a0 = ws.ca[cc];
+        const uint32_t ch_t = (cc + 1 < nc ? ws.ct[cc + 1] : tot_t) - t0, ch_a = (cc + 1 < nc ? ws.ca[cc + 1] : tot_a) - a0;
+        for (uint32_t j = tid; j < n; j += kBlock) {
+            const uint32_t it = t0 + (j + 1 < n ? ws.bt[base + j + 1] : ch_t);
+            const uint32_t ia = a0 + (j + 1 < n ? ws.ba[base + j + 1] : ch_a);
+            if (it > room_t || ia > room_a) atomicMin(&s_cut, base + j);
+        }
+    }
+    __syncthreads();
+    const uint32_t cut = s_cut, fb = nb ? ws.first[0] : kNoBatch, fe = nb ? ws.first[1] : kNoBatch;
+    uint32_t s = fb < cut ? fb : cut;
+    s = fe < s ? fe : s;  // (<= nb)
+    uint32_t stop;
+    if (s == nb) stop = pos.batch + nb < n_batches ? DV_WIRE_STOP_WINDOW : DV_WIRE_STOP_END;
+    else if (s == fb) stop = DV_WIRE_STOP_MALFORMED;
+    else if (s == cut) stop = DV_WIRE_STOP_CAPACITY;
+    else stop = DV_WIRE_STOP_BATCH;  // (or STALE, below)
+    const uint64_t E = pos.batch_id != kNoBatchId ? pos.batch_id : (nb ? ws.bid[0] : kNoBatchId);
+    const uint32_t m0 = s == 0 ? pos.msg : 0;
+    uint32_t run = 0;
+    if (stop == DV_WIRE_STOP_BATCH) {
+        const uint64_t id = ws.bid[s];
+        if (id == E) {
+            run = ws.brun[s];
+            if (ws.bflag[s] == kRunEarlier) stop = DV_WIRE_STOP_STALE;
+        } else if (id < E) {
+            stop = DV_WIRE_STOP_STALE;
+        }
+    }
+    const bool ends = stop == DV_WIRE_STOP_BATCH || stop == DV_WIRE_STOP_STALE;
+    const uint32_t k = s + (ends ? 1u : 0u);  // mbufs whose runs are taken (<= nb)
+    const uint32_t full = k / kWireChunk;
+    uint32_t mx = 0;
+    for (uint32_t i = tid; i < full; i += kBlock) mx = ws.cm[i] > mx ? ws.cm[i] : mx;
+    for (uint32_t j = full * kWireChunk + tid; j < k; j += kBlock) mx = ws.bm[j] > mx ? ws.bm[j] : mx;
+    atomicMax(&s_max, mx);
+    __syncthreads();
+    if (tid != 0) return;
+    const uint32_t n_txn = pos.n_txn + (k == nb ? tot_t : ws.ct[full] + ws.bt[k]);
+    const uint64_t n_acc = pos.n_acc + (k == nb ? tot_a : ws.ca[full] + ws.ba[k]);
+    const uint32_t rdone = pos.rdone + (k == nb ? tot_r : ws.cr[full] + ws.br[k]);
+    WireCalvinRes r;
+    r.pos.batch = stop == DV_WIRE_STOP_END ? n_batches : pos.batch + s;
+    r.pos.msg = s == nb ? 0u : m0 + run;
+    r.pos.n_txn = n_txn;
+    r.pos.rdone = rdone;
+    r.pos.n_acc = n_acc;
+    r.pos.batch_id = s > 0 || run > 0 ? E : pos.batch_id;  // (every mbuf taken whole holds a message behind the cursor)
+    r.pos.max_txn_acc = s_max > pos.max_txn_acc ? s_max : pos.max_txn_acc;
+    r.pos.stop = stop;
+    r.status = stop == DV_WIRE_STOP_END ? DV_OK
+               : stop == DV_WIRE_STOP_MALFORMED || stop == DV_WIRE_STOP_STALE ? DV_ERR_ARG
+               : stop == DV_WIRE_STOP_CAPACITY && n_txn == 0 ? DV_ERR_ARG
+                                                             : DV_WIRE_MORE;
+    r.n_emit = ends && run == 0 ? s : k;  // (an empty run: nothing of mbuf s to decode)
+    r.last_end = ends && run > 0 ? m0 + run : kNoBatch;
+    r.pad_ = 0;
+    *ws.res = r;
+    out.txn_begin[n_txn] = (uint32_t)n_acc;  // (n_txn <= max_txn, n_acc <= max_acc < 2^32)
+    if (out.n_acc_dev) *out.n_acc_dev = (uint32_t)n_acc;
+}
+
+// the window's first n_emit mbufs, a wave each: lane m message m from the
+// cursor (the last mbuf: below the plan's last_end) -- a CL_QRY's txn index a
+// wave prefix over the CL_QRY flags, its boundary and reply fields; then all
+// lanes the requests in order, consecutive lanes, consecutive accesses.
+// Everything lands behind the epoch's n_txn_in txns and n_acc_in accesses.
+__global__ __launch_bounds__(kBlock) void k_wire_emit_calvin(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
+                                                             const uint64_t *__restrict__ off, uint32_t first,
+                                                             uint32_t msg0, dv_wire_dev_out out, uint32_t n_txn_in,
+                                                             uint32_t n_acc_in, WireCalvinWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint32_t s_rq[kWireWave][64];
+    __shared__ uint16_t s_p2[kWireWave][64], s_tx[kWireWave][64];  // message m's request count's offset, txns before it
+    const uint32_t n_emit = ws.res->n_emit;
+    if (blockIdx.x * kWireWave >= n_emit) return;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t b = blockIdx.x * kWireWave + wave;
+    const bool live = b < n_emit;  // (checked by k_wire_check_calvin: its span and every field are good)
+    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
+    if (live) {
+        const uint64_t o0 = off[first + b];
+        st.sh = stage_batch(buf + o0, (uint32_t)(off[first + b + 1] - o0), s_img[wave], lane);
+    }
+    __syncthreads();
+    uint32_t src = 0, my_n = 0, my_p2 = 0, my_q = 0, t0 = 0, a0 = 0;
+    uint64_t cst = 0, tid = 0;
+    if (live) {
+        src = st.u32(4);
+        const uint32_t count = st.u32(8), last_end = b + 1 == n_emit ? ws.res->last_end : kNoBatch;
+        const uint32_t m0 = b == 0 ? msg0 : 0, mend = last_end < count ? last_end : count;
+        t0 = n_txn_in + ws.ct[b / kWireChunk] + ws.bt[b];
+        a0 = n_acc_in + ws.ca[b / kWireChunk] + ws.ba[b];
+        if (lane >= m0 && lane < mend) {
+            const uint32_t mo = ws.moff[(uint64_t)b * kWireCalvinMaxMsg + lane];
+            if (st.u32(mo) == DV_WIRE_CL_QRY) {
+                my_q = 1;
+                tid = st.u64(mo + kCalTxnId);
+                cst = st.u64(mo + kCalHdr);
+                my_p2 = mo + kCalFixed + st.u32(mo + kCalHdr + 8) * 8u;
+                my_n = st.u32(my_p2);
+            }
+        }
+    }
+    const uint32_t rq_in = wave_incl_sum(my_n, lane), q_in = wave_incl_sum(my_q, lane);
+    const uint32_t tot_rq = __shfl(rq_in, 63, 64);
+    s_rq[wave][lane] = rq_in - my_n;
+    s_p2[wave][lane] = (uint16_t)my_p2;
+    s_tx[wave][lane] = (uint16_t)(q_in - my_q);
+    __syncthreads();
+    if (!live) return;
+    if (my_q) {
+        const uint32_t t = t0 + q_in - 1u;
+        out.txn_begin[t] = a0 + rq_in - my_n;
+        if (out.txn_id) out.txn_id[t] = tid;  // the sequencer's
+        if (out.client_startts) out.client_startts[t] = cst;
+        if (out.return_node) out.return_node[t] = src;
+    }
+    for (uint32_t r = lane; r < tot_rq; r += 64) {
+        const uint32_t m = last_le64(s_rq[wave], r);
+        const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
+        const uint32_t acctype = st.u32(ro);
+        const uint64_t key = st.u64(ro + 8);
+        const uint32_t a = a0 + r;
+        if (out.recs32) out.recs32[a] = (uint32_t)key | (acctype == DV_WR ? AR_WR : 0u);
+        out.keys[a] = key;
+        out.types[a] = (uint8_t)acctype;
+        out.acc_txn[a] = t0 + s_tx[wave][m];
+        if (out.owner) out.owner[a] = (uint8_t)(key % cfg.part_cnt);  // key_to_part
+    }
+}
+
+uint64_t wire_calvin_ws_bytes(uint32_t nb) {
+    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
+    // (every array's size a multiple of 8 bytes: the ids and moff first, the words, the bytes last)
+    return 64 + 8 + n * 8 + n * kWireCalvinMaxMsg * 2 + 3 * ((n + 1) & ~1ull) * 4 + 4 * ((nc + 1) & ~1ull) * 4 +
+           3 * ((n + 7) & ~7ull);
+}
+
+WireCalvinWs wire_calvin_ws_carve(void *base, uint32_t nb) {
+    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
+    const uint64_t n2 = (n + 1) & ~1ull, nc2 = (nc + 1) & ~1ull, n8 = (n + 7) & ~7ull;
+    WireCalvinWs w;
+    char *p = static_cast<char *>(base);
+    w.res = reinterpret_cast<WireCalvinRes *>(p);
+    p += 64;
+    w.first = reinterpret_cast<uint32_t *>(p);
+    p += 8;
+    w.bid = reinterpret_cast<uint64_t *>(p);
+    p += n * 8;
+    w.moff = reinterpret_cast<uint16_t *>(p);
+    p += n * kWireCalvinMaxMsg * 2;
+    uint32_t **words[] = {&w.bt, &w.ba, &w.br};
+    for (uint32_t **q : words) {
+        *q = reinterpret_cast<uint32_t *>(p);
+        p += n2 * 4;
+    }
+    uint32_t **chunks[] = {&w.ct, &w.ca, &w.cr, &w.cm};
+    for (uint32_t **q : chunks) {
+        *q = reinterpret_cast<uint32_t *>(p);
+        p += nc2 * 4;
+    }
+    uint8_t **bytes[] = {&w.bm, &w.brun, &w.bflag};
+    for (uint8_t **q : bytes) {
+        *q = reinterpret_cast<uint8_t *>(p);
+        p += n8;
+    }
+    return w;
+}
+
+void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
+                             const uint64_t *off, uint32_t nb, uint32_t n_batches, const dv_wire_dev_out &out,
+                             const dv_wire_calvin_pos &pos, const WireCalvinWs &ws) {
+    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
+    (void)hipMemsetAsync(ws.first, 0xFF, 2 * sizeof(uint32_t), s);  // kNoBatch, both
+    if (nb) {
+        DV_LAUNCH(k_wire_check_calvin, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, buf_len, off, pos.batch,
+                  pos.msg, nb, ws);
+        DV_LAUNCH(k_wire_scan_calvin, nc, kBlock, 0, s, ws, nb, pos.batch_id);
+    }
+    DV_LAUNCH(k_wire_plan_calvin, 1, kBlock, 0, s, ws, nb, n_batches, nc, out, pos);
+}
+
+void launch_wire_emit_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
+                             uint32_t nb, const dv_wire_dev_out &out, const dv_wire_calvin_pos &pos,
+                             const WireCalvinWs &ws) {
+    if (!nb) return;
+    DV_LAUNCH(k_wire_emit_calvin, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, off, pos.batch, pos.msg,
+              out, pos.n_txn, (uint32_t)pos.n_acc, ws);
 }
 
 // ---- the committed txns' reply fields, compacted in txn order

@@ -169,6 +169,17 @@ class WireDevResult(ctypes.Structure):  # dv_wire_dev_result
                 ("max_txn_acc", ctypes.c_uint32), ("n_acc", ctypes.c_uint64), ("next_txn", ctypes.c_uint64)]
 
 
+class WireCalvinPos(ctypes.Structure):  # dv_wire_calvin_pos: cursor and epoch totals of dv_wire_ingest_device_calvin
+    _fields_ = [("batch", ctypes.c_uint32), ("msg", ctypes.c_uint32), ("n_txn", ctypes.c_uint32),
+                ("rdone", ctypes.c_uint32), ("n_acc", ctypes.c_uint64), ("batch_id", ctypes.c_uint64),
+                ("max_txn_acc", ctypes.c_uint32), ("stop", ctypes.c_uint32)]
+
+
+# dv_wire_calvin_pos::stop (DV_WIRE_STOP_*)
+WIRE_STOP_END, WIRE_STOP_BATCH, WIRE_STOP_CAPACITY, WIRE_STOP_WINDOW, WIRE_STOP_MALFORMED, WIRE_STOP_STALE = range(6)
+WIRE_NO_BATCH_ID = (1 << 64) - 1
+
+
 class LoopTrackDesc(ctypes.Structure):  # dv_loop_track (dv_closed_loop_track; dvcc.LoopTrack owns the arrays)
     _fields_ = [("ids", ctypes.POINTER(ctypes.c_void_p)), ("n_bufs", ctypes.c_uint32),
                 ("first_epoch", ctypes.c_uint32), ("log", ctypes.c_void_p), ("log_cap", ctypes.c_uint32),
@@ -286,6 +297,8 @@ SIGNATURES = [
     ("dv_wire_ingest_device_tpcc", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
                                                   ctypes.c_uint32, _P(WireTpccDevOut), ctypes.c_uint64,
                                                   _P(WireDevResult)]),
+    ("dv_wire_ingest_device_calvin", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                                    _P(WireDevOut), _P(WireCalvinPos)]),
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),

@@ -10,7 +10,9 @@ packed the same way from the epoch's commit bytes.  DeviceWireIngress does
 the YCSB ingress on the device instead (dv_wire_ingest_device): the receive
 queue's bytes in, a device-resident epoch out.  TpccDeviceWireIngress does the
 same for TPC-C client batches (dv_wire_ingest_device_tpcc), every message
-expanded to its access list on the device.
+expanded to its access list on the device.  CalvinDeviceWireIngress takes
+CALVIN sequencer streams (dv_wire_ingest_device_calvin, YCSB): cut at the
+message where the batch id changes, appended stream by stream in node order.
 """
 import ctypes
 from dataclasses import dataclass
@@ -363,6 +365,129 @@ class DeviceWireIngress(_DeviceReplies):
                                           max_txn_acc=res.max_txn_acc)
         ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
         return ep, res.n_taken, res.status
+
+
+class CalvinDeviceWireIngress:
+    """dv_wire_ingest_device_calvin over device buffers of max_txn txns and
+    max_acc accesses on `engine`'s context (YCSB under CALVIN): sequencer
+    streams, cut at message granularity, appended into one open epoch.  An
+    epoch is one sequencer batch per sequencer in origin-major order:
+    feed_buffer once per stream, in node order (or sequence(), which does
+    that), then take().  The epoch's tensors are the ingress's own: the feeds
+    after the next take() overwrite them."""
+
+    def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
+                 device="cuda"):
+        import torch
+        self.engine = engine
+        self.cfg = L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
+        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
+        A, T = max(1, self.max_acc), self.max_txn
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
+        self.txn_begin = new(T + 1, torch.int32)
+        self.keys, self.types, self.acc_txn = new(A, torch.int64), new(A, torch.uint8), new(A, torch.int32)
+        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
+        self.return_node = new(T, torch.int32)
+        self._dev = device
+        self._held = []
+        self.status = L.DV_OK
+        self._open()
+
+    def _open(self):
+        """an empty epoch: no txn, no batch id yet"""
+        self.n_txn = self.n_acc = self.rdone = self.max_txn_acc = 0
+        self.batch_id = None
+
+    def feed_buffer(self, buf, off, pos=None):
+        """Appends one sequencer's stream -- mbufs back to back in buf (a torch
+        uint8 device tensor, or a numpy array, uploaded) at offsets off (u64
+        [n + 1]) -- to the open epoch, from the cursor pos: None for the
+        stream's start, a (mbuf, message) pair, or the WireCalvinPos an
+        earlier call returned.  Returns the updated WireCalvinPos: the new
+        cursor, the epoch's totals and `stop`, why the call ended
+        (WIRE_STOP_END: the stream is consumed; BATCH: the message at the
+        cursor opens the next batch -- take() the epoch once every sequencer's
+        stream got there; CAPACITY: the epoch is full; MALFORMED / STALE: the
+        mbuf / message at the cursor is refused).  self.status holds the C
+        status.  A window's end (WIRE_STOP_WINDOW) is called again here."""
+        buf, off = _DeviceReplies._upload(buf, off, self._dev)
+        self.engine._after_torch()
+        p = L.WireCalvinPos()
+        if pos is not None:
+            p.batch, p.msg = (pos.batch, pos.msg) if isinstance(pos, L.WireCalvinPos) else pos
+        p.n_txn, p.rdone, p.n_acc, p.max_txn_acc = self.n_txn, self.rdone, self.n_acc, self.max_txn_acc
+        p.batch_id = L.WIRE_NO_BATCH_ID if self.batch_id is None else self.batch_id
+        q = lambda t: t.data_ptr()  # noqa: E731
+        out = L.WireDevOut(self.max_txn, 0, self.max_acc, q(self.txn_begin), None, None, q(self.keys), q(self.types),
+                           q(self.acc_txn), None, q(self.txn_id), q(self.client_startts), q(self.return_node))
+        while True:
+            p.stop = 0xFFFFFFFF
+            rc = L.lib().dv_wire_ingest_device_calvin(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(),
+                                                      buf.numel(), off.data_ptr(), off.numel() - 1,
+                                                      ctypes.byref(out), ctypes.byref(p))
+            if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or p.stop == 0xFFFFFFFF:
+                L.check(rc, "dv_wire_ingest_device_calvin")  # (refused before any launch, or a HIP failure)
+            if p.stop != L.WIRE_STOP_WINDOW:
+                break
+        self._held.append((buf, off))  # (the decode may still read them when this returns)
+        self.status = rc
+        self.n_txn, self.rdone, self.n_acc, self.max_txn_acc = p.n_txn, p.rdone, p.n_acc, p.max_txn_acc
+        self.batch_id = None if p.batch_id == L.WIRE_NO_BATCH_ID else int(p.batch_id)
+        return p
+
+    def take(self):
+        """Closes the open epoch and returns it: a DeviceEpoch of exact size
+        over the ingress's tensors (written on the engine's stream: run it
+        there), with batch_id, rdone (one per sequencer when the batch is
+        complete), txn_begin and the device reply arrays."""
+        n, a = self.n_txn, self.n_acc
+        ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n,
+                                      max_txn_acc=self.max_txn_acc)
+        ep.batch_id, ep.rdone = self.batch_id, self.rdone
+        ep.txn_begin = self.txn_begin[:n + 1]
+        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
+        self._held = self._held[-2:]
+        self._open()
+        return ep
+
+    def sequence(self, streams, cursors=None):
+        """One Calvin epoch from every sequencer's stream: streams is [(buf,
+        off)] in node order, cursors where each stands (None: all at their
+        start).  Every stream is fed up to the end of its batch (BATCH) or of
+        its bytes (END); anything else raises.  Returns (epoch, cursors), the
+        cursors for the next batch."""
+        cursors = [None] * len(streams) if cursors is None else list(cursors)
+        nxt = []
+        for (buf, off), cur in zip(streams, cursors):
+            p = self.feed_buffer(buf, off, cur)
+            if p.stop not in (L.WIRE_STOP_BATCH, L.WIRE_STOP_END):
+                raise L.DvccError(self.status, f"dv_wire_ingest_device_calvin: stop {p.stop} at mbuf {p.batch}, "
+                                               f"message {p.msg}")
+            nxt.append((p.batch, p.msg))
+        return self.take(), nxt
+
+    def respond(self, ep):
+        """The CALVIN_ACK batches (bytes) of the epoch, one ack per txn to its
+        sequencer: every txn is acknowledged, so the reply fields go to the
+        host packer (dv_wire_respond) as they are."""
+        n = ep.n_txn
+        if not n:
+            return []
+        self.engine._after_torch()
+        e = L.WireEpoch()
+        e.n_txn, e.max_txn = n, n
+        e.batch_id = L.WIRE_NO_BATCH_ID if ep.batch_id is None else ep.batch_id
+        tid, rn = ep.txn_id.cpu().numpy(), ep.return_node.cpu().numpy()
+        e.txn_id, e.return_node = tid.ctypes.data, rn.ctypes.data
+        # (a batch holds (MSG_MAX - 12) // message size acks; one partial batch per destination)
+        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 8 + 7 * 8 + 4)
+        max_b = n // per + len(np.unique(rn)) + 1
+        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
+        off = np.zeros(max_b + 1, np.uint64)
+        nb = ctypes.c_uint32()
+        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), None, _ptr(out), len(out),
+                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
+        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

@@ -60,7 +60,8 @@
  *                               message.cpp:921-949, 1057-1110) packed as MessageThread does
  *                               (transport/msg_thread.cpp:53-111)
  *   dv_wire_ingest_device /     the same receive path for YCSB / TPC-C client batches
- *   dv_wire_ingest_device_tpcc /  already in device memory, into a device epoch; the
+ *   dv_wire_ingest_device_tpcc /  already in device memory, into a device epoch (and
+ *   dv_wire_ingest_device_calvin / CALVIN sequencer streams, cut at their batch ids); the
  *   dv_wire_reply_fields_device committed txns' reply fields compacted for dv_wire_respond
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
@@ -1126,10 +1127,12 @@ int dv_wire_respond(const dv_wire_cfg *cfg, const dv_wire_epoch *ep, const uint8
                     uint64_t cap, uint64_t *batch_off, uint32_t max_batches, uint32_t *n_batches);
 
 /* ---- the same ingress on the device (dvcc_wire.hip): a receive queue's bytes
- * as they are, in device memory, into a device-resident epoch.  Without
- * CALVIN only (its batch-id sequencing stays on the host decoder: DV_ERR_ARG).
+ * as they are, in device memory, into a device-resident epoch.
  * dv_wire_ingest_device takes YCSB batches and refuses TPC-C, which has an
- * entry of its own below (dv_wire_ingest_device_tpcc).
+ * entry of its own below (dv_wire_ingest_device_tpcc); both refuse CALVIN
+ * (DV_ERR_ARG), whose sequencer streams -- cut at message granularity -- go
+ * through dv_wire_ingest_device_calvin (YCSB; TPC-C under CALVIN stays on the
+ * host decoder).
  * The caller's device output buffers and their capacities: */
 typedef struct dv_wire_dev_out {
     uint32_t max_txn, pad_;      /* 1 .. 2^24                                              */
@@ -1232,6 +1235,91 @@ typedef struct dv_wire_tpcc_dev_out {
 int dv_wire_ingest_device_tpcc(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
                                const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
                                const dv_wire_tpcc_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res);
+/* ---- CALVIN sequencer streams on the device (YCSB).  A sequencer's stream is
+ * cut at message granularity, not mbuf granularity: MessageThread packs per
+ * destination until an mbuf is full, so one mbuf routinely holds the tail of
+ * batch e (ending in RDONE) followed by the head of batch e + 1.  An epoch is
+ * one sequencer batch per sequencer, concatenated origin-major; the call below
+ * appends one stream's share of it from a (mbuf, message) cursor.
+ * Why the call stopped (pos->stop) and the status it returns: */
+#define DV_WIRE_STOP_END       0  /* the stream is consumed                         -> DV_OK        */
+#define DV_WIRE_STOP_BATCH     1  /* the message at the cursor names a later batch  -> DV_WIRE_MORE */
+#define DV_WIRE_STOP_CAPACITY  2  /* the mbuf at the cursor does not fit            -> DV_WIRE_MORE
+                                     (DV_ERR_ARG while the epoch holds no txn: it would never fit) */
+#define DV_WIRE_STOP_WINDOW    3  /* the call's window of mbufs ended               -> DV_WIRE_MORE */
+#define DV_WIRE_STOP_MALFORMED 4  /* the mbuf at the cursor is refused whole         -> DV_ERR_ARG   */
+#define DV_WIRE_STOP_STALE     5  /* the message at the cursor names an earlier batch -> DV_ERR_ARG */
+
+typedef struct dv_wire_calvin_pos {     /* host memory, in/out */
+    uint32_t batch, msg;      /* cursor: the next message is message `msg` of mbuf `batch`
+                                 (batch == n_batches, msg == 0: consumed)                  */
+    uint32_t n_txn, rdone;    /* the epoch so far, as dv_wire_epoch keeps them             */
+    uint64_t n_acc;
+    uint64_t batch_id;        /* UINT64_MAX: none yet                                      */
+    uint32_t max_txn_acc;     /* longest txn so far                                        */
+    uint32_t stop;            /* out: DV_WIRE_STOP_*                                       */
+} dv_wire_calvin_pos;
+
+/* Appends to the epoch *pos describes, over out's buffers (dv_wire_dev_out;
+ * txn_begin, keys, types and acc_txn required -- a CALVIN epoch takes no prefix
+ * path and no device-side access count; recs32, owner, txn_id, client_startts,
+ * return_node and n_acc_dev optional, n_acc_dev receiving the epoch's total;
+ * recs32 needs cfg->synth_table_size <= 2^31 as in dv_wire_ingest_device).
+ * Txn t of the call is epoch txn pos->n_txn + t and its accesses start at
+ * pos->n_acc: txn_begin[0 .. pos->n_txn) and everything below pos->n_acc belong
+ * to earlier calls and are not written; acc_txn and txn_begin carry epoch
+ * numbering; txn_begin[n_txn] = n_acc of the new totals closes the epoch.
+ * Several sequencers' streams become one epoch in origin-major order by one
+ * call per stream, in node order, on the same buffers: the result equals the
+ * concatenation (dvcc.sequence) of the host-decoded per-sequencer epochs.
+ *
+ * E is pos->batch_id if set, else the batch id of the message at the cursor.
+ * Messages are taken in stream order exactly as dv_wire_decode_batches takes
+ * them with cfg->calvin = 1: a CL_QRY becomes a txn with txn_id = the
+ * message's (the sequencer's), its client_startts, and return_node = the
+ * mbuf's src; an RDONE of batch E counts in rdone.  One difference, the
+ * sibling device entries': capacity is tested per mbuf, not per message.
+ * The run of an mbuf is its messages from the cursor (`msg` for the first
+ * mbuf, 0 after it) up to, not including, the first whose batch id is not E.
+ * Mbuf by mbuf, the first stopper in stream order decides:
+ *   1. the mbuf is malformed -- an off that decreases or points past buf_len,
+ *      a cursor msg at or past its count, or whatever dv_wire_open refuses
+ *      under a CALVIN cfg (header, count, exact fill of the length, an rtype
+ *      other than CL_QRY / RDONE, a batch id of UINT64_MAX on any message,
+ *      partitions, request count, RD / WR, keys; every count compared as the
+ *      64-bit value it is before any multiply): stop = MALFORMED, the cursor
+ *      at its (batch, msg), nothing of it taken, no byte of it in an output;
+ *   2. the run's txns or accesses, added to the epoch's, pass max_txn /
+ *      max_acc: stop = CAPACITY, the cursor at its (batch, msg), nothing of it
+ *      taken; DV_ERR_ARG while the epoch still holds no txn.  An empty run
+ *      never fails this;
+ *   3. the run is shorter than what is left of the mbuf: the run is taken, the
+ *      cursor goes to the message behind it; stop = BATCH if that message's
+ *      id is above E, STALE if below (the host decoder also keeps what it
+ *      decoded before a stale message);
+ *   4. the call's window of mbufs is exhausted (it bounds the per-call words,
+ *      and is at least (max_txn - pos->n_txn) + 1 mbufs, so a stream without
+ *      RDONE-only mbufs always reaches another stopper): stop = WINDOW, the
+ *      cursor at the next mbuf -- call again with the same pos;
+ *   5. no mbuf is left: stop = END, the cursor (n_batches, 0).
+ * A malformed mbuf behind another stopper is not reported by this call.
+ * On return *pos holds the new cursor, totals, batch_id (E once any message
+ * was taken, otherwise unchanged), max_txn_acc and stop; the status mapped as
+ * above is returned.  Nothing is written at or past txn n_txn (txn_begin:
+ * n_txn + 1) or access n_acc.  Queued on the context's stream; the call waits
+ * for the result record alone, and an epoch over the buffers runs on the same
+ * context with no other synchronisation.
+ * Refused before any launch (DV_ERR_ARG, *pos untouched): a null pointer,
+ * cfg->calvin == 0, a workload other than DV_YCSB (TPC-C under CALVIN stays on
+ * the host decoder), zero part_cnt / node_cnt, a missing required array, keys
+ * / types / acc_txn not all three, recs32 with a table above 2^31, max_txn
+ * outside 1 .. 2^24, max_acc >= 2^32, pos->batch > n_batches, msg != 0 at
+ * batch == n_batches, pos->n_txn > max_txn, pos->n_acc > max_acc.  A context
+ * in the middle of an epoch: DV_ERR_STATE. */
+int dv_wire_ingest_device_calvin(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                                 const uint64_t *off, uint32_t n_batches, const dv_wire_dev_out *out,
+                                 dv_wire_calvin_pos *pos);
+
 /* The reply fields of the committed txns (commit[t] != 0, device bytes) of an
  * epoch ingested on the device: txn_id / client_startts / return_node
  * (device, [n_txn]) compacted in txn order into out_* (device or host-mapped,
