@@ -1223,14 +1223,21 @@ struct LocalXport final : Xport {
                                          hipMemcpyDeviceToDevice, s), "copy"));
         return retire(s);
     }
+    // all_to_allv and all_to_allv_segs are one collective: every sender picks
+    // its own form (run_group's `direct` is a rank's own decision), as ncclSend
+    // pairs with ncclAllToAllv over RCCL, so a peer's part for this rank is
+    // read from whichever form it published
+    const uint8_t *from(int q) const {
+        const LocalGroup::Slot &p = g->slot[q];
+        return p.segs ? p.segs[r] : p.send + p.sd[r];
+    }
     int all_to_allv(const uint8_t *send, const size_t *sc, const size_t *sd, uint8_t *recv, const size_t *rc,
                     const size_t *rd, hipStream_t s) override {
         (void)sc;
+        g->slot[r].segs = nullptr;
         CHK(publish(send, sd, s));
         for (int q = 0; q < g->P; q++)
-            if (rc[q])
-                CHK(hip_fail2(hipMemcpyAsync(recv + rd[q], g->slot[q].send + g->slot[q].sd[r], rc[q],
-                                             hipMemcpyDeviceToDevice, s), "copy"));
+            if (rc[q]) CHK(hip_fail2(hipMemcpyAsync(recv + rd[q], from(q), rc[q], hipMemcpyDeviceToDevice, s), "copy"));
         return retire(s);
     }
     int all_to_allv_segs(const uint8_t *const *send, const size_t *sc, uint8_t *recv, const size_t *rc,
@@ -1239,9 +1246,7 @@ struct LocalXport final : Xport {
         g->slot[r].segs = send;  // (read by the peers after publish's barrier)
         CHK(publish(nullptr, nullptr, s));
         for (int q = 0; q < g->P; q++)
-            if (rc[q])
-                CHK(hip_fail2(hipMemcpyAsync(recv + rd[q], g->slot[q].segs[r], rc[q], hipMemcpyDeviceToDevice, s),
-                              "copy"));
+            if (rc[q]) CHK(hip_fail2(hipMemcpyAsync(recv + rd[q], from(q), rc[q], hipMemcpyDeviceToDevice, s), "copy"));
         return retire(s);
     }
     template <class T>

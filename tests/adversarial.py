@@ -88,8 +88,14 @@ def _const(text, name):
 def structural_constants():
     """kTile (the synchronous pass's tile of 32-bit elements and of 64-bit
     ones), kAsyncCap, the tail capacities, kBlock / kCarryTpb, kHotRows and
-    the Bloom filter's bits, from csrc/."""
+    the Bloom filter's bits, and the partitioned path's kXTile (a tile of
+    landed accesses), kIlTxns / kIlOwn (k_il_move_tb's tile of txns and its
+    LDS index), kMaxPos (the longest txn) and kRouteBlocks, from csrc/."""
     rounds, internal, prefix = _src("dvcc_rounds.hip"), _src("dvcc_internal.h"), _src("dvcc_prefix.hip")
+    comm = _src("dvcc_comm.hip")
+    assert re.search(r"constexpr\s+uint32_t\s+kXTile\s*=\s*kBlock\s*\*\s*kXIPT\s*;", comm)
+    il = re.search(r"constexpr\s+uint32_t\s+kIlTxns\s*=\s*(\d+)\s*,\s*kIlOwn\s*=\s*(\d+)\s*;", comm)
+    max_pos = re.search(r"constexpr\s+uint32_t\s+kMaxPos\s*=\s*1u\s*<<\s*(\d+)\s*;", internal)
     t32 = int(re.search(r"kThreads\s*=\s*sizeof\(EIn\)\s*==\s*4\s*\?\s*(\d+)", rounds).group(1))
     tail = re.search(r"struct TailGeo\s*\{\s*static constexpr int kIPT = sizeof\(E\) == 4 \? (\d+) : (\d+);", rounds)
     tail_threads = _const(internal, "kTailThreads")
@@ -105,6 +111,11 @@ def structural_constants():
         kHotRows=1 << _define(prefix, "DVCC_HOT_LOG"),
         kBloomBits=1 << _define(prefix, "DVCC_BLOOM_LOG"),
         kRoundLog=_const(internal, "kRoundLog"),
+        kXTile=_const(internal, "kBlock") * _const(comm, "kXIPT"),
+        kIlTxns=int(il.group(1)),
+        kIlOwn=int(il.group(2)),
+        kMaxPos=1 << int(max_pos.group(1)),
+        kRouteBlocks=_const(internal, "kRouteBlocks"),
     )
 
 
@@ -334,3 +345,242 @@ def contiguous_chunks(e, world):
         out.append(Epoch(e.keys[tb[a]:tb[b]].copy(), e.types[tb[a]:tb[b]].copy(),
                          (tb[a:b + 1] - tb[a]).astype(np.uint32)))
     return out, tpr
+
+
+def strided_chunks(e, world):
+    """`e` dealt out txn by txn: origin q gets sequence slots q, q + world,
+    ... as its txns 0, 1, ... (ceil(n_txn / world) slots each, the last ones
+    of the later origins missing when world does not divide n_txn), txn ids
+    local to the chunk.  dvcc.sequence_position of the chunks is `e` again, as
+    dvcc.sequence of contiguous_chunks (each padded to tpr txns) is."""
+    tpr = (e.n_txn + world - 1) // world
+    tb = e.txn_begin.astype(np.int64)
+    lens = np.diff(tb)
+    out = []
+    for q in range(world):
+        ids = np.arange(q, e.n_txn, world)
+        ltb = np.zeros(len(ids) + 1, np.int64)
+        ltb[1:] = np.cumsum(lens[ids])
+        idx = np.repeat(tb[ids] - ltb[:-1], lens[ids]) + np.arange(int(ltb[-1]))
+        out.append(Epoch(e.keys[idx].copy(), e.types[idx].copy(), ltb.astype(np.uint32)))
+    return out, tpr
+
+
+def trim_tail(b):
+    """`b` without its trailing empty txns: the batch an origin hands over
+    when its last sequence slots hold no txn (its real, smaller n_txn, down to
+    0); the slots it leaves are empty txns of the epoch, which commit."""
+    n = np.flatnonzero(np.diff(b.txn_begin.astype(np.int64)))
+    return Epoch(b.keys, b.types, b.txn_begin[:(int(n[-1]) + 2) if n.size else 1].copy())
+
+
+def pad_tail(b, tpr):
+    """`b` with empty txns appended up to tpr txns (what dvcc.sequence needs
+    to give every origin its tpr slots)"""
+    return Epoch(b.keys, b.types, np.concatenate([b.txn_begin, np.full(tpr - b.n_txn, b.txn_begin[-1], np.uint32)]))
+
+
+# ---- family 9: Ragged ladder(slots, stride, row_of).  `slots` lists the
+# epoch's sequence slots: EMPTY (a txn without accesses), a pad count p >= 0 (a
+# ladder txn), or ONE (a single private access).  The k-th ladder txn is
+# [W row_of(k), W row_of(k + 1)] followed by p accesses of private rows, 2 + p
+# <= kMaxPos; a private row is priv0 + stride * i for the epoch's i-th private
+# access (priv0: the first multiple of stride past the ladder's rows), used
+# once in the whole epoch, a write when i % 3 == 0 and a read otherwise.
+# NO_WAIT / WAIT_DIE / OCC: private rows never conflict and no row repeats
+# inside a txn (no H9), so the ladder decides as family 1 -- the k-th ladder
+# txn commits iff k is even -- and empty and ONE txns commit.  CALVIN: all
+# commit.  Under `row % world` ownership row_of and stride place the rows
+# (ownership()).
+EMPTY, ONE = None, -1
+
+
+def ragged_ladder(slots, stride, row_of):
+    kmax = structural_constants()["kMaxPos"]
+    slots = list(slots)
+    lens = np.array([0 if s is EMPTY else 1 if s == ONE else 2 + s for s in slots], np.int64)
+    lad = np.array([s is not EMPTY and s != ONE for s in slots], bool)
+    assert lens.max(initial=0) <= kmax and (lens[lad] >= 2).all()
+    L = int(lad.sum())
+    k = np.arange(L, dtype=np.int64)
+    tb = np.zeros(len(slots) + 1, np.int64)
+    tb[1:] = np.cumsum(lens)
+    n = int(tb[-1])
+    keys = np.zeros(n, np.int64)
+    types = np.zeros(n, np.uint8)
+    priv = np.ones(n, bool)
+    a = tb[:-1][lad]  # the ladder txns' first accesses
+    ladder_rows = np.asarray(row_of(np.arange(L + 1, dtype=np.int64)), np.int64)
+    assert L == 0 or (np.diff(ladder_rows) > 0).all()
+    keys[a], keys[a + 1] = ladder_rows[:-1], ladder_rows[1:]
+    types[a] = types[a + 1] = WR
+    priv[a] = priv[a + 1] = False
+    i = np.arange(int(priv.sum()), dtype=np.int64)
+    priv0 = (int(ladder_rows[-1]) // stride + 1) * stride
+    keys[priv] = priv0 + stride * i
+    types[priv] = (i % 3 == 0).astype(np.uint8)
+    e = _mk(lens, keys, types)
+    c = _ones(len(slots))
+    c[lad] = k % 2 == 0
+    exp = {cc: c.copy() for cc in LOCKING + ("OCC",)}
+    exp["CALVIN"] = _ones(len(slots))
+    return Case(e, priv0 + stride * len(i) + 1, exp)
+
+
+OWNERSHIPS = ("spread", "part0", "skip_last")
+
+
+def ownership(kind, world):
+    """(row_of, stride) of a ragged ladder under `row % world` ownership:
+    spread     ladder row k, private rows consecutive: every partition alike
+    part0      every row a multiple of world: partition 0 owns everything
+    skip_last  ladder rows on partitions 0 .. world - 2 in turn, private rows
+               on partition 0: partition world - 1 owns nothing that is used"""
+    if kind == "spread":
+        return (lambda k: k), 1
+    if kind == "part0":
+        return (lambda k: world * k), world
+    assert kind == "skip_last" and world >= 2
+    return (lambda k: k + k // (world - 1)), world
+
+
+# ---- the shapes: per-origin slot lists, laid out as the global epoch in
+# either order so that its cut (contiguous_chunks for origin-major,
+# strided_chunks for position-major, each batch then trim_tail'ed) hands every
+# origin exactly its list
+def arrange(per_origin, order, tpr=None):
+    world = len(per_origin)
+    tpr = tpr or max(1, max(len(s) for s in per_origin))
+    grid = [list(s) + [EMPTY] * (tpr - len(s)) for s in per_origin]
+    if order == "position":
+        return [grid[q][j] for j in range(tpr) for q in range(world)]
+    assert order == "origin"
+    return [grid[q][j] for q in range(world) for j in range(tpr)]
+
+
+def cut(e, world, order):
+    """the origins' batches of global epoch `e` (trailing empty txns dropped)
+    and txns_per_rank"""
+    parts, tpr = strided_chunks(e, world) if order == "position" else contiguous_chunks(e, world)
+    return [trim_tail(p) for p in parts], tpr
+
+
+def _fill(total, unit):
+    """pad counts of ladder txns of `unit` accesses holding `total` accesses
+    in all, the last txn sized to land the total"""
+    kmax = structural_constants()["kMaxPos"]
+    assert 2 <= unit < kmax and (total == 0 or total >= 2)
+    lens = [unit] * (total // unit)
+    rem = total - unit * len(lens)
+    if rem >= 2 or (rem and not lens):
+        lens.append(rem)
+    elif rem:
+        lens[-1] += 1
+    return [n - 2 for n in lens]
+
+
+def _spread(total, n):
+    """pad counts of n ladder txns holding `total` accesses as evenly as it goes"""
+    kmax = structural_constants()["kMaxPos"]
+    lens = np.full(n, total // n)
+    lens[:total % n] += 1
+    assert lens.min() >= 2 and lens.max() <= kmax
+    return [int(x) - 2 for x in lens]
+
+
+def _segment(total):
+    """one origin's batch of `total` accesses; where it spans more than a tile
+    of kXTile, a txn of kMaxPos accesses sits across the first tile edge"""
+    K = structural_constants()
+    X, M = K["kXTile"], K["kMaxPos"]
+    if total < X + M:
+        return _fill(total, 31)
+    return _fill(X - M // 2, 31) + [M - 2] + _fill(total - X - M // 2, 31)
+
+
+def segment_sizes():
+    X = structural_constants()["kXTile"]
+    return [X - 1, X, X + 1, 2 * X + 1]
+
+
+def segment_edge_group(world, order, own="spread"):
+    """Segment edges: a group's `world` epochs.  In epoch e one origin has no
+    accesses at all (no txns: it stands first, in the middle, last, in turn
+    over the epochs) and the others hold kXTile - 1, kXTile, kXTile + 1 and
+    2 * kXTile + 1 accesses in turn -- what k_group_txn_count,
+    k_group_txn_ids and k_il_move tile.  Returns (cases, txns_per_rank)."""
+    sizes = segment_sizes()
+    zero_at = [0, world // 2, world - 1]
+    per_epoch, i = [], 0
+    for e in range(world):
+        per = []
+        for q in range(world):
+            if q == zero_at[e % 3]:
+                per.append([])
+            else:
+                per.append(_segment(sizes[i % len(sizes)]))
+                i += 1
+        per_epoch.append(per)
+    tpr = max(len(s) for per in per_epoch for s in per)
+    row_of, stride = ownership(own, world)
+    return [ragged_ladder(arrange(per, order, tpr), stride, row_of) for per in per_epoch], tpr
+
+
+MOVE_KINDS = ("search", "exact", "over", "empties", "small")
+
+
+def _move_tile(kind, nj):
+    """nj txns of one k_il_move_tb tile holding: `small` 2 accesses each;
+    `exact` kIlOwn accesses; `over` kIlOwn + 1; `search` an empty txn and then
+    three of kMaxPos accesses, over and over (3 * kIlOwn at nj = kIlTxns:
+    the binary search, with equal starts before every long txn); `empties`
+    nothing"""
+    K = structural_constants()
+    if kind == "empties":
+        return [EMPTY] * nj
+    if kind == "small":
+        return [0] * nj
+    if kind == "search":
+        return [EMPTY if j % 4 == 0 else K["kMaxPos"] - 2 for j in range(nj)]
+    return _spread(K["kIlOwn"] + (kind == "over"), nj)
+
+
+def move_tile_group(world, tpr, order="position", own="spread", first=0):
+    """Move tiles: a group's `world` epochs of `tpr` txns per origin.  Every
+    origin's batch is made of tiles of kIlTxns txns; the tiles of at least
+    kIlTxns - 1 txns take MOVE_KINDS in turn (from `first`) over the group,
+    a shorter last tile is `small`.  Returns (cases, txns_per_rank)."""
+    T = structural_constants()["kIlTxns"]
+    row_of, stride = ownership(own, world)
+    cases, i = [], first
+    for e in range(world):
+        per = []
+        for q in range(world):
+            slots = []
+            for j0 in range(0, tpr, T):
+                nj = min(T, tpr - j0)
+                if nj >= T - 1:
+                    slots += _move_tile(MOVE_KINDS[i % len(MOVE_KINDS)], nj)
+                    i += 1
+                else:
+                    slots += _move_tile("small", nj)
+            per.append(slots)
+        cases.append(ragged_ladder(arrange(per, order, tpr), stride, row_of))
+    return cases, tpr
+
+
+def wave_mix(world, own="spread", shift=0):
+    """Wave mix: runs of 64 consecutive sequence slots (what one wave of the
+    route's txn walk takes) mixing 0-, 1-, 2- and kMaxPos-access txns in a
+    pattern of period 7, then 63 empty txns beside one of kMaxPos, then 64 of
+    kMaxPos, then slots up to a multiple of `world`.  `shift` moves the
+    pattern (a group's epochs differ)."""
+    M = structural_constants()["kMaxPos"]
+    pat = [EMPTY, M - 2, ONE, 0, EMPTY, 0, M - 2]
+    slots = [pat[(i + shift) % len(pat)] for i in range(64 * 4)]
+    slots += [EMPTY] * (63 - shift % 63) + [M - 2] + [EMPTY] * (shift % 63)
+    slots += [M - 2] * 64
+    tail = [0, ONE, M - 2]
+    slots += [tail[i % 3] for i in range(-len(slots) % world)]
+    row_of, stride = ownership(own, world)
+    return ragged_ladder(slots, stride, row_of)

@@ -888,24 +888,41 @@ def test_epoch_groups_asynchronous_deciders(cc, async_iters, prefix, batch):
 
 
 @pytest.mark.gpu
-def test_epoch_groups_bad_boundaries_fail_collectively():
-    """A batch whose txn_begin falls inside (handed over as a DeviceEpoch with
-    a tampered boundary): its sender's check fails the group with DV_ERR_ARG
-    on every rank, no row changes, and the next group runs normally."""
+@pytest.mark.parametrize("tamper", ["nonzero_start", "descending", "short_end", "past_end", "zero_txns"])
+@pytest.mark.parametrize("position", [False, True])
+def test_epoch_groups_bad_boundaries_fail_collectively(position, tamper):
+    """A batch whose boundaries are wrong (handed over as a DeviceEpoch with a
+    tampered txn_begin) to a decider on another rank: the receiver's check of
+    the landed boundaries (tbx_bad -- in k_tb_origin origin-major, in
+    k_il_begin position-major) fails the group with DV_ERR_ARG on every rank,
+    no row changes, and the next group runs normally.  One tampering per
+    clause of the check: the first boundary not 0, a boundary above the next,
+    the last one below the batch's access count and above it; and a batch of 0
+    txns (no boundaries at all) that carries accesses."""
     world, rows_pp, n_txn = 2, 1 << 12, 1500
     gen = dvcc.YCSBQueryGenerator(rows_pp * world, part_cnt=world, zipf_theta=0.9, part_per_txn=2,
                                   strict_ppt=1, mpr=0.3)
     engines = _engine_group(dvcc.NO_WAIT, world, rows_pp, n_txn, mode=2)
     for eng in engines:
         eng.set_prefix(300)
-        eng.comm_set_mode(2 | dvcc._lib.DV_COMM_POSITION_ORDER)
+        eng.comm_set_mode(2 | (dvcc._lib.DV_COMM_POSITION_ORDER if position else 0))
     before = [eng.read_table(0, rows_pp) for eng in engines]
     homes = [[dvcc.DeviceEpoch(gen.gen(n_txn, dvcc.epoch_seed(r, 120 + e), r)) for e in range(world)]
              for r in range(world)]
     bad = dvcc.DeviceEpoch(gen.gen(n_txn, dvcc.epoch_seed(1, 130), 1))
-    bad.txn_begin[9] = bad.txn_begin[11] + 1  # (not rising)
+    assert bad.n_txn == n_txn  # (a full batch: its last boundary is checked, never an address)
+    if tamper == "nonzero_start":
+        bad.txn_begin[0] = 1
+    elif tamper == "descending":
+        bad.txn_begin[9] = bad.txn_begin[11] + 1  # (not rising)
+    elif tamper == "short_end":
+        bad.txn_begin[n_txn] = bad.n_acc - 1
+    elif tamper == "past_end":
+        bad.txn_begin[n_txn] = bad.n_acc + 1
+    else:  # its accesses as raw device arrays that claim no txn: no boundaries travel for it
+        bad = dvcc.DeviceEpoch.from_tensors(bad.keys, bad.types, bad.acc_txn, 0, max_txn_acc=bad.max_txn_acc)
     bad_homes = [list(h) for h in homes]
-    bad_homes[1][0] = bad
+    bad_homes[1][0] = bad  # (rank 1's batch of epoch 0, which rank 0 decides)
     res = _run_group_epochs(engines, bad_homes, n_txn)
     for r, x in enumerate(res):
         assert isinstance(x, dvcc.DvccError) and x.code == dvcc._lib.DV_ERR_ARG, (r, x)
