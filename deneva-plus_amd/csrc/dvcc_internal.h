@@ -8,6 +8,7 @@
 #include <chrono>
 
 #include "dvcc.h"
+#include "dvcc_wire_layout.h"
 
 namespace dvcc {
 
@@ -675,24 +676,8 @@ void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn,
                            const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const RefillTrack &trk,
                            const RefillBackoff &bo);
 
-// ---- Deneva client batches decoded on the device (dvcc_wire.hip)
-// k_wire_check takes kWireWave batches per workgroup (a wave each), the scan
-// kWireChunk batches per chunk, the reply compaction kReplyTile txns per tile.
-constexpr uint32_t kWireWave = 4;
-constexpr uint32_t kWireChunk = 256 * 12;  // (block_chunk_scan256's register path)
-constexpr uint32_t kWireMaxMsg = 40;       // messages of a 4,096-byte batch (100 bytes each at least)
-constexpr uint32_t kReplyTile = 256;
-// the per-call words of nb batches (device): carved from one allocation
-struct WireWs {
-    uint32_t *bt, *ba;      // [nb] txns / accesses per batch, then their prefix inside the chunk
-    uint8_t *bm;            // [nb] the batch's longest txn
-    uint16_t *moff;         // [nb * kWireMaxMsg] message offsets inside the batch
-    uint32_t *ct, *ca, *cm; // [chunks] per chunk: txns, accesses (then their prefixes), longest txn
-    uint32_t *first_bad;    // one word: the first malformed batch
-    dv_wire_dev_result *res;
-};
-uint64_t wire_ws_bytes(uint32_t nb);
-WireWs wire_ws_carve(void *base, uint32_t nb);
+// ---- Deneva client batches decoded on the device (dvcc_wire.hip); the
+// per-call words, their layout and the tiles' sizes: dvcc_wire_layout.h
 // batches [first, first + nb) of buf checked, scanned and planned (the result
 // record complete in ws.res, the closing boundary and *n_acc_dev written) ...
 void launch_wire_plan(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
@@ -720,40 +705,15 @@ void launch_wire_plan_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_
 void launch_wire_emit_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
                            const uint64_t *off, uint32_t first, uint32_t nb, const dv_wire_tpcc_dev_out &out,
                            uint64_t next_txn, const WireWs &ws);
-// CALVIN sequencer streams (dv_wire_ingest_device_calvin): the header carries
-// batch_id (84 bytes), an RDONE is the header alone, so an mbuf holds up to
-// kWireCalvinMaxMsg messages -- the path's own stride, kWireMaxMsg stays the
-// siblings'.  A CL_QRY is 108 bytes at least: at most 37 txns an mbuf, and
-// 24 bytes a request, fewer than kWireCalvinBatchAcc accesses; a call looks at
-// kMaxTxn + 1 mbufs at most, so every running sum stays in 32 bits.
-constexpr uint32_t kWireCalvinMaxMsg = 48;
+// CALVIN sequencer streams (dv_wire_ingest_device_calvin).  A CL_QRY is 108
+// bytes at least: at most 37 txns an mbuf, and 24 bytes a request, fewer than
+// kWireCalvinBatchAcc accesses; a call looks at kMaxTxn + 1 mbufs at most, so
+// every running sum stays in 32 bits.
 constexpr uint32_t kWireCalvinBatchAcc = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / 24 + 1;
 static_assert(((uint64_t)kMaxTxn + 1) * kWireCalvinBatchAcc < (1ull << 32), "a call's accesses fit 32 bits");
 static_assert(((uint64_t)kMaxTxn + 1) * kWireCalvinMaxMsg < (1ull << 32), "a call's txns and RDONEs fit 32 bits");
-// what the plan leaves for the host (pos, status) and for the emit
-struct WireCalvinRes {
-    dv_wire_calvin_pos pos;
-    int32_t status;
-    uint32_t n_emit;    // mbufs of the window the emit decodes
-    uint32_t last_end;  // the last of them: its messages below this one (its count: all)
-    uint32_t pad_;
-};
-static_assert(sizeof(WireCalvinRes) <= 64, "the context's pinned words");
-struct WireCalvinWs {
-    uint32_t *bt, *ba, *br;       // [nb] txns / accesses / RDONEs of the mbuf's run, then their prefix inside the chunk
-    uint64_t *bid;                // [nb] the batch id of the mbuf's first message from the cursor
-    uint8_t *bm;                  // [nb] the run's longest txn
-    uint8_t *brun;                // [nb] the run's length in messages
-    uint8_t *bflag;               // [nb] the message behind the run: 0 none, 1 a later batch, 2 an earlier one
-    uint16_t *moff;               // [nb * kWireCalvinMaxMsg] message offsets inside the mbuf
-    uint32_t *ct, *ca, *cr, *cm;  // [chunks] per chunk: txns, accesses, RDONEs (then their prefixes), longest txn
-    uint32_t *first;              // two words: the first malformed mbuf, the first where the batch ends
-    WireCalvinRes *res;
-};
-uint64_t wire_calvin_ws_bytes(uint32_t nb);
-WireCalvinWs wire_calvin_ws_carve(void *base, uint32_t nb);
 // mbufs [pos.batch, pos.batch + nb) of buf checked from the cursor, scanned and
-// planned (ws.res complete, the closing boundary and *n_acc_dev written) ...
+// planned (ws.cres complete, the closing boundary and *n_acc_dev written) ...
 void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
                              const uint64_t *off, uint32_t nb, uint32_t n_batches, const dv_wire_dev_out &out,
                              const dv_wire_calvin_pos &pos, const WireCalvinWs &ws);

@@ -180,16 +180,15 @@ struct dv_ctx {
     uint32_t bo_nb = 0;
     uint32_t *gc_tb = nullptr;                       // dv_epoch_group_carry: a batch's ranges (2 x max_txn)
     uint32_t *gc_tot = nullptr;                      // ... 3 totals per batch (kMaxGroupBatches)
-    // dv_wire_ingest_device / dv_wire_reply_fields_device (dvcc_wire.hip): the
-    // per-call words of wire_nb batches, the reply compaction's tile counts,
-    // and the pinned words the two entries read back (the result record, the count)
+    // dv_wire_ingest_device* / dv_wire_reply_fields_device (dvcc_wire.hip): an
+    // ingest's per-call words, whatever the dialect (a call's words are dead
+    // once its emit has run), and the reply compaction's tile counts, each with
+    // its capacity in bytes; the pinned words the entries read back
     uint8_t *wire_ws = nullptr;
-    uint32_t wire_nb = 0;
-    uint8_t *wire_cws = nullptr;                     // dv_wire_ingest_device_calvin's words of wire_cnb mbufs
-    uint32_t wire_cnb = 0;
-    uint32_t *reply_bc = nullptr;
-    uint32_t reply_nt = 0;
-    dv_wire_dev_result *wire_h = nullptr;
+    uint64_t wire_ws_cap = 0;
+    uint8_t *reply_bc = nullptr;
+    uint64_t reply_bc_cap = 0;
+    uint8_t *wire_h = nullptr;                       // kWireResBytes for the plan's record, then the reply count
     hipEvent_t wire_ev = nullptr;
     DvComm *comm = nullptr;                          // RCCL communicator (dv_comm_init)
     uint32_t round_tag = 0;                          // descriptor tag of the last pass
@@ -739,7 +738,7 @@ void dv_close(dv_ctx *c) {
                     c->d_tables, c->d_commit, c->d_txn, c->d_grant, c->d_tb, c->split_err,
                     c->d_args, c->d_oid, c->tp_dsnap,
                     c->row_state, c->b_status, c->b_tlen, c->b_map, c->kinfo, c->ktsum, c->kill_bits, c->gc_tb, c->gc_tot,
-                    c->wire_ws, c->wire_cws, c->reply_bc,
+                    c->wire_ws, c->reply_bc,
                     c->hslot[0].acc, c->hslot[0].tb, c->hslot[1].acc, c->hslot[1].tb};
     for (void *b : bufs) dfree(b);
     for (auto &h : c->hslot) {
@@ -3944,23 +3943,47 @@ int dv_tpcc_epoch_run(dv_ctx *c, const dv_access *acc, uint64_t n_acc, const uin
 }
 
 // ---- Deneva client batches decoded on the device (dvcc_wire.hip)
-// the context's per-call words for nb batches, its pinned result record and event
-static int wire_ws_prepare(dv_ctx *c, uint32_t nb) {
-    if (nb > c->wire_nb || !c->wire_ws) {  // (no captured graph names these words)
-        HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(c->wire_ws);
-        c->wire_ws = nullptr;
-        c->wire_nb = 0;
-        int r = dalloc(&c->wire_ws, wire_ws_bytes(nb));
-        if (r) return r;
-        c->wire_nb = nb ? nb : 1;
-    }
-    if (!c->wire_h) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
-    }
+extern "C++" {  // (templates among them)
+// a device scratch of the context grown to `bytes` (no captured graph names
+// it; what is queued on the stream may still use the old one)
+static int scratch_reserve(dv_ctx *c, uint8_t **p, uint64_t *cap, uint64_t bytes) {
+    if (*p && bytes <= *cap) return DV_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dfree(*p);
+    int r = dalloc(p, bytes);  // (null where it fails)
+    *cap = r ? 0 : bytes;
+    return r;
+}
+
+// the context's pinned words and the event behind which they are read
+static int wire_host_ready(dv_ctx *c) {
+    if (c->wire_h) return DV_OK;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), kWireResBytes + 8, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
     return DV_OK;
 }
+
+// behind a plan: its record to the pinned words, an event behind the copy,
+// the emit launched, and the wait for the record alone -- the emit runs on
+template <class Emit>
+static int wire_record_then_emit(dv_ctx *c, const void *d_res, size_t bytes, Emit emit) {
+    HIPCHK(hipMemcpyAsync(c->wire_h, d_res, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
+    emit();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventSynchronize(c->wire_ev));
+    return DV_OK;
+}
+
+// an ingest's words for nb batches, laid out by `layout` in the context's scratch
+template <class Ws, class Layout>
+static int wire_words(dv_ctx *c, uint32_t nb, Ws *ws, Layout layout) {
+    int r = scratch_reserve(c, &c->wire_ws, &c->wire_ws_cap, layout(nullptr, nb, *ws));
+    if (!r) r = wire_host_ready(c);
+    if (!r) layout(c->wire_ws, nb, *ws);
+    return r;
+}
+}  // extern "C++"
 
 int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
                           const uint64_t *off, uint32_t n_batches, uint32_t first_batch,
@@ -3982,16 +4005,15 @@ int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf,
     // and a stopper lies among the first max_txn + 1: the call looks no
     // further (and every sum of 40 txns / 170 accesses a batch stays in 32 bits).
     const uint32_t nb = std::min(n_batches - first_batch, out->max_txn + 1);
-    int r = wire_ws_prepare(c, nb);
+    WireWs ws;
+    int r = wire_words(c, nb, &ws, wire_ws_layout);
     if (r) return r;
-    const WireWs ws = wire_ws_carve(c->wire_ws, c->wire_nb);
     launch_wire_plan(c->stream, *cfg, buf, buf_len, off, first_batch, nb, n_batches, *out, next_txn, ws);
-    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(dv_wire_dev_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
-    launch_wire_emit(c->stream, *cfg, buf, off, first_batch, nb, *out, next_txn, ws);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone: the emit runs on
-    *res = *c->wire_h;
+    r = wire_record_then_emit(c, ws.res, sizeof(*res), [&] {
+        launch_wire_emit(c->stream, *cfg, buf, off, first_batch, nb, *out, next_txn, ws);
+    });
+    if (r) return r;
+    std::memcpy(res, c->wire_h, sizeof(*res));
     return res->status;
 }
 
@@ -4019,17 +4041,16 @@ int dv_wire_ingest_device_tpcc(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t 
     // kWireTpccMaxTxn + 1 of them keep every sum of a batch's 20 txns and
     // fewer than kWireTpccBatchAcc accesses in 32 bits.
     const uint32_t nb = std::min(n_batches - first_batch, out->max_txn + 1);
-    int r = wire_ws_prepare(c, nb);
+    WireWs ws;
+    int r = wire_words(c, nb, &ws, wire_ws_layout);
     if (r) return r;
     const dv_tpcc_params tp = *cfg->tpcc;
-    const WireWs ws = wire_ws_carve(c->wire_ws, c->wire_nb);
     launch_wire_plan_tpcc(c->stream, *cfg, tp, buf, buf_len, off, first_batch, nb, n_batches, *out, next_txn, ws);
-    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(dv_wire_dev_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
-    launch_wire_emit_tpcc(c->stream, *cfg, tp, buf, off, first_batch, nb, *out, next_txn, ws);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone, as above
-    *res = *c->wire_h;
+    r = wire_record_then_emit(c, ws.res, sizeof(*res), [&] {
+        launch_wire_emit_tpcc(c->stream, *cfg, tp, buf, off, first_batch, nb, *out, next_txn, ws);
+    });
+    if (r) return r;
+    std::memcpy(res, c->wire_h, sizeof(*res));
     return res->status;
 }
 
@@ -4053,26 +4074,14 @@ int dv_wire_ingest_device_calvin(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_
     // At most kMaxTxn + 1 mbufs keep every running sum in 32 bits.
     const uint32_t window = std::max(out->max_txn - pos->n_txn + 1, 256u);
     const uint32_t nb = std::min(n_batches - pos->batch, window);
-    if (nb > c->wire_cnb || !c->wire_cws) {  // (no captured graph names these words)
-        HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(c->wire_cws);
-        c->wire_cws = nullptr;
-        c->wire_cnb = 0;
-        int r = dalloc(&c->wire_cws, wire_calvin_ws_bytes(nb));
-        if (r) return r;
-        c->wire_cnb = nb ? nb : 1;
-    }
-    if (!c->wire_h) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
-    }
-    const WireCalvinWs ws = wire_calvin_ws_carve(c->wire_cws, c->wire_cnb);
+    WireCalvinWs ws;
+    int r = wire_words(c, nb, &ws, wire_calvin_ws_layout);
+    if (r) return r;
     launch_wire_plan_calvin(c->stream, *cfg, buf, buf_len, off, nb, n_batches, *out, *pos, ws);
-    HIPCHK(hipMemcpyAsync(c->wire_h, ws.res, sizeof(WireCalvinRes), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(c->wire_ev, c->stream));
-    launch_wire_emit_calvin(c->stream, *cfg, buf, off, nb, *out, *pos, ws);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventSynchronize(c->wire_ev));  // the record alone, as above
+    r = wire_record_then_emit(c, ws.cres, sizeof(WireCalvinRes), [&] {
+        launch_wire_emit_calvin(c->stream, *cfg, buf, off, nb, *out, *pos, ws);
+    });
+    if (r) return r;
     const WireCalvinRes *h = reinterpret_cast<const WireCalvinRes *>(c->wire_h);
     *pos = h->pos;
     return h->status;
@@ -4090,24 +4099,15 @@ int dv_wire_reply_fields_device(dv_ctx *c, const uint8_t *commit, uint32_t n_txn
     if (c->phase != 0) return DV_ERR_STATE;
     HIPCHK(hipSetDevice(c->cfg.device));
     const uint32_t nt = reply_tiles(n_txn);
-    if (nt > c->reply_nt || !c->reply_bc) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(c->reply_bc);
-        c->reply_bc = nullptr;
-        c->reply_nt = 0;
-        int r = dalloc(&c->reply_bc, (uint64_t)nt + 1);
-        if (r) return r;
-        c->reply_nt = nt;
-    }
-    if (!c->wire_h) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->wire_h), 64, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->wire_ev, hipEventDisableTiming));
-    }
+    int r = scratch_reserve(c, &c->reply_bc, &c->reply_bc_cap, ((uint64_t)nt + 1) * sizeof(uint32_t));
+    if (!r) r = wire_host_ready(c);
+    if (r) return r;
+    uint32_t *bc = reinterpret_cast<uint32_t *>(c->reply_bc);
     launch_reply_fields(c->stream, commit, n_txn, txn_id, client_startts, return_node, out_txn_id,
-                        out_client_startts, out_return_node, c->reply_bc);
+                        out_client_startts, out_return_node, bc);
     HIPCHK(hipGetLastError());
-    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(c->wire_h + 1);
-    HIPCHK(hipMemcpyAsync(h_cnt, c->reply_bc + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(c->wire_h + kWireResBytes);
+    HIPCHK(hipMemcpyAsync(h_cnt, bc + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *n_out = *h_cnt;
     return DV_OK;

@@ -2,24 +2,28 @@
 //
 // What csrc/wire.cpp does message by message on one core (dv_wire_open's
 // checks, dv_wire_decode's arrays) for a receive queue's bytes already in
-// device memory: YCSB CL_QRY batches, not CALVIN, taken at whole-batch
-// granularity into a device-resident epoch (include/dvcc.h,
-// dv_wire_ingest_device).  A batch is at most 4,096 bytes and a short chain of
+// device memory, taken into a device-resident epoch (include/dvcc.h,
+// dv_wire_ingest_device*).  A batch is at most 4,096 bytes and a short chain of
 // variable-length messages, so a wave takes one: its bytes staged in LDS,
-// the chain walked once (at most 40 links), then every partition and request
-// checked or scattered by all lanes.
-//   k_wire_check   per batch {txns, accesses, longest txn}, the message
+// the chain walked once (at most 48 links), then every partition and request
+// checked or scattered by all lanes.  Three dialects, four launches each:
+//   k_wire_check*  per batch {txns, accesses, longest txn}, the message
 //                  offsets, and the first malformed batch
-//   k_wire_scan    per chunk of kWireChunk batches: prefixes inside the chunk
-//   k_wire_plan    one workgroup: the chunks' prefixes, the first batch that
+//   k_wire_scan*   per chunk of kWireChunk batches: prefixes inside the chunk
+//   k_wire_plan*   one workgroup: the chunks' prefixes, the first batch that
 //                  does not fit, the result record, the closing boundary
-//   k_wire_emit    the taken batches' boundaries, reply fields and accesses
-// TPC-C CL_QRY batches (dv_wire_ingest_device_tpcc) take the same scan and
-// plan between k_wire_check_tpcc and k_wire_emit_tpcc, which expand every
-// message to its access list as dv_tpcc_expand does.
-// CALVIN sequencer streams (dv_wire_ingest_device_calvin, YCSB) have the four
-// launches as kernels of their own, k_wire_*_calvin: the header carries
-// batch_id, RDONE ends a batch, and the epoch is cut at a message.
+//   k_wire_emit*   the taken batches' boundaries, reply fields and accesses
+// YCSB CL_QRY batches (dv_wire_ingest_device) are taken whole.  TPC-C CL_QRY
+// batches (dv_wire_ingest_device_tpcc) take the same scan and plan between
+// k_wire_check_tpcc and k_wire_emit_tpcc, which expand every message to its
+// access list as dv_tpcc_expand does.  CALVIN sequencer streams
+// (dv_wire_ingest_device_calvin, YCSB; k_wire_*_calvin) have a header that
+// carries batch_id, RDONE ends a batch, and the epoch is cut at a message.
+// What the dialects share is written once, in the helpers of the first
+// namespace below: the staging prologues, the chain walk, the partition and
+// request loops, the txn fields, the plan's capacity cut.  A dialect is a
+// compile-time parameter (Client, Calvin), never a switch inside a kernel; a
+// helper with a barrier is reached by every wave of its block, live or not.
 // And, for the replies, the committed txns' fields compacted in txn order
 // (k_reply_count / k_reply_scan / k_reply_emit, like the carry-over's).
 // The byte stream has no alignment (COPY_BUF): fields are assembled from the
@@ -35,11 +39,24 @@ constexpr uint32_t kWireMsgMax = DV_WIRE_MSG_MAX;
 // in (up to 15 bytes in front) to the line of its last, and one line more so
 // a field's last word may be read past it
 constexpr uint32_t kStageQ = (kWireMsgMax + 15 + 15) / 16 + 1;
-constexpr uint32_t kMsgHdr = 76;       // rtype, txn_id, mq_time, 7 latencies (Message::mget_size, not CALVIN)
-constexpr uint32_t kMsgFixed = 92;     // ... client_startts, the partition count
 constexpr uint32_t kReqBytes = 24;     // sizeof(ycsb_request)
 constexpr uint32_t kReqMax = 128;      // the engine's longest txn (kMaxPos)
 constexpr uint32_t kNoBatch = 0xFFFFFFFFu;
+constexpr uint32_t kCalTxnId = 4, kCalBatchId = 12;  // CALVIN header offsets
+constexpr uint64_t kNoBatchId = ~0ull;
+
+// A dialect's message (Message::mget_size): kHdr bytes of rtype, txn_id,
+// [batch_id,] mq_time, 7 latencies; a CL_QRY goes on to kFixed with
+// client_startts and the partition count.  kStride: messages a batch may hold,
+// the stride of WireWs::moff.  kRdone: an RDONE, the header alone, is a message.
+struct Client {
+    static constexpr uint32_t kHdr = 76, kFixed = 92, kStride = kWireMaxMsg;
+    static constexpr bool kRdone = false;
+};
+struct Calvin {
+    static constexpr uint32_t kHdr = 84, kFixed = 100, kStride = kWireCalvinMaxMsg;
+    static constexpr bool kRdone = true;
+};
 
 struct Stage {
     const uint32_t *w;  // the image's words
@@ -71,6 +88,15 @@ __device__ __forceinline__ uint32_t last_le64(const uint32_t *pre, uint32_t r) {
     return k;
 }
 
+__device__ __forceinline__ uint32_t wave_max(uint32_t mx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t y = __shfl_xor(mx, o, 64);
+        mx = y > mx ? y : mx;
+    }
+    return mx;
+}
+
 // batch b of the call: its bytes, or bad where off decreases, points past the
 // buffer, or the length is outside [12, 4096]
 __device__ __forceinline__ bool batch_span(const uint64_t *off, uint32_t b, uint64_t buf_len, uint64_t &o0,
@@ -82,89 +108,294 @@ __device__ __forceinline__ bool batch_span(const uint64_t *off, uint32_t b, uint
     return true;
 }
 
+// ---- staging: a wave and the batch it holds
+struct WaveBatch {
+    uint32_t lane, wave, b, len;
+    bool live, bad;  // a batch of the call; its span refused (nothing staged)
+    Stage st;
+};
+
+// wave `wave` of the block takes batch b of the call's nb: nothing staged yet
+__device__ __forceinline__ WaveBatch wave_batch(uint4 (*img)[kStageQ], uint32_t nb) {
+    WaveBatch w;
+    w.lane = threadIdx.x & 63, w.wave = threadIdx.x >> 6;
+    w.b = blockIdx.x * kWireWave + w.wave;
+    w.live = w.b < nb;
+    w.bad = false;
+    w.len = 0;
+    w.st = Stage{reinterpret_cast<const uint32_t *>(img[w.wave]), 0};
+    return w;
+}
+
+// The check's prologue: the wave's batch staged where its span is good.  Ends
+// in a barrier: every wave of the block comes here, live or not.
+__device__ __forceinline__ WaveBatch stage_wave_batch(uint4 (*img)[kStageQ], const uint8_t *buf, uint64_t buf_len,
+                                                      const uint64_t *off, uint32_t first, uint32_t nb) {
+    WaveBatch w = wave_batch(img, nb);
+    uint64_t o0 = 0;
+    w.bad = w.live && !batch_span(off, first + w.b, buf_len, o0, w.len);
+    if (w.live && !w.bad) w.st.sh = stage_batch(buf + o0, w.len, img[w.wave], w.lane);
+    __syncthreads();
+    return w;
+}
+
+// The emit's prologue, for a block with a taken batch at least (the caller left
+// with the whole block otherwise): batch b below `taken` was checked, its span
+// and every field are good.  Ends in a barrier, as above.
+__device__ __forceinline__ WaveBatch stage_taken_batch(uint4 (*img)[kStageQ], const uint8_t *buf,
+                                                       const uint64_t *off, uint32_t first, uint32_t taken) {
+    WaveBatch w = wave_batch(img, taken);
+    if (w.live) {
+        const uint64_t o0 = off[first + w.b];
+        w.len = (uint32_t)(off[first + w.b + 1] - o0);
+        w.st.sh = stage_batch(buf + o0, w.len, img[w.wave], w.lane);
+    }
+    __syncthreads();
+    return w;
+}
+
+// ---- the chain
+// message m as lane m keeps it: its offset and rtype; a CL_QRY's partition
+// count, the offset `bo` behind its partitions and the count n its body named
+struct Msg {
+    uint32_t off, rt, np, n, bo;
+};
+
+// create_messages' asserts on {dest, src, count} (message.cpp:39-41)
+template <class D>
+__device__ __forceinline__ bool open_header(const Stage &st, const dv_wire_cfg &cfg, uint32_t &count) {
+    count = st.u32(8);
+    return st.u32(0) == cfg.node_id && st.u32(4) != cfg.node_id && count != 0 && count <= D::kStride;
+}
+
+// Every lane walks the batch's `count` messages; false for whatever
+// dv_wire_open refuses in the chain, which must fill exactly `len` bytes.
+// Every length is compared as the 64-bit count it is before it is multiplied:
+// a count of 2^61 + 1 fails its limit, it never reaches n * 24.  body(bo, n)
+// checks a CL_QRY's bytes from bo on, sets n and returns the message's end
+// (0: refused).  Lane m is left message m in `mine`.
+template <class D, class Body>
+__device__ __forceinline__ bool walk_chain(const Stage &st, uint32_t len, uint32_t count, uint32_t lane, Msg &mine,
+                                           Body body) {
+    uint32_t pos = DV_WIRE_HDR;
+    for (uint32_t m = 0; m < count; m++) {
+        if (pos + (D::kRdone ? D::kHdr : D::kFixed) > len) return false;
+        Msg g{pos, st.u32(pos), 0, 0, 0};
+        // (a client's message is a query whatever it says: its rtype is tested beside its count, not in front)
+        const bool query = !D::kRdone || g.rt == DV_WIRE_CL_QRY;
+        if (D::kRdone && (st.u64(pos + kCalBatchId) == kNoBatchId || (!query && g.rt != DV_WIRE_RDONE) ||
+                          (query && pos + D::kFixed > len)))
+            return false;
+        uint32_t end = pos + D::kHdr;
+        if (query) {
+            const uint64_t np = st.u64(pos + D::kHdr + 8);
+            if (g.rt != DV_WIRE_CL_QRY || np > DV_TPCC_MAX_PARTS) return false;
+            g.np = (uint32_t)np;
+            g.bo = pos + D::kFixed + g.np * 8u;
+            end = body(g.bo, g.n);
+            if (!end) return false;
+        }
+        if (lane == m) mine = g;
+        pos = end;
+    }
+    return pos == len;
+}
+
+// ---- a batch's flat loops: pre[m] things before message m, tot in all
+// a partition named at or above part_cnt (mo: message m's offset)
+template <class D>
+__device__ __forceinline__ bool parts_wrong(const Stage &st, const uint32_t *pp, const uint16_t *mo, uint32_t tot_pp,
+                                            uint32_t part_cnt, uint32_t lane) {
+    bool wrong = false;
+    for (uint32_t q = lane; q < tot_pp; q += 64) {
+        const uint32_t m = last_le64(pp, q);
+        wrong |= st.u64(mo[m] + D::kFixed + (q - pp[m]) * 8u) >= part_cnt;
+    }
+    return wrong;
+}
+
+// a request that is not RD / WR of a key inside the table (p2: the offset of message m's request count)
+__device__ __forceinline__ bool requests_wrong(const Stage &st, const uint32_t *rq, const uint16_t *p2,
+                                               uint32_t tot_rq, uint64_t table_size, uint32_t lane) {
+    bool wrong = false;
+    for (uint32_t r = lane; r < tot_rq; r += 64) {
+        const uint32_t m = last_le64(rq, r);
+        const uint32_t ro = p2[m] + 8u + (r - rq[m]) * kReqBytes;
+        wrong |= st.u32(ro) > DV_WR || st.u64(ro + 8) >= table_size;
+    }
+    return wrong;
+}
+
+// the batch's requests in order -- consecutive lanes, consecutive accesses --
+// from access a0 on; a request of message m belongs to txn t0 + txn_of(m)
+template <class TxnOf>
+__device__ __forceinline__ void emit_requests(const Stage &st, const uint32_t *rq, const uint16_t *p2, uint32_t tot_rq,
+                                              uint32_t t0, uint32_t a0, const dv_wire_dev_out &out, uint32_t part_cnt,
+                                              uint32_t lane, TxnOf txn_of) {
+    for (uint32_t r = lane; r < tot_rq; r += 64) {
+        const uint32_t m = last_le64(rq, r);
+        const uint32_t ro = p2[m] + 8u + (r - rq[m]) * kReqBytes;
+        const uint32_t acctype = st.u32(ro);
+        const uint64_t key = st.u64(ro + 8);
+        const uint32_t a = a0 + r;
+        if (out.recs32) out.recs32[a] = (uint32_t)key | (acctype == DV_WR ? AR_WR : 0u);
+        if (out.keys) {
+            out.keys[a] = key;
+            out.types[a] = (uint8_t)acctype;
+            out.acc_txn[a] = t0 + txn_of(m);
+        }
+        if (out.owner) out.owner[a] = (uint8_t)(key % part_cnt);  // key_to_part
+    }
+}
+
+// The YCSB check of a dialect up to its verdict, for every wave of the block
+// (a barrier inside): the header, a cursor m0 below the count, the chain of
+// queries of at most cfg.max_req (128) requests, then every partition and
+// request.  True: the batch is refused whole.  (A bad batch's lanes hold zeros
+// or a part of the chain: its tables are not read.)
+struct YcsbTables {
+    uint32_t rq[kWireWave][64], pp[kWireWave][64];  // requests / partitions before message m
+    uint16_t mo[kWireWave][64], p2[kWireWave][64];  // message m's offset, its request count's
+};
+template <class D>
+__device__ __forceinline__ bool ycsb_batch_bad(const WaveBatch &w, const dv_wire_cfg &cfg, uint32_t m0,
+                                               YcsbTables &t, uint32_t &count, Msg &my, uint32_t &tot_rq) {
+    const Stage &st = w.st;
+    const bool parse = w.live && !w.bad;
+    bool bad = w.bad;
+    if (parse) {
+        const uint32_t lim = cfg.max_req && cfg.max_req < kReqMax ? cfg.max_req : kReqMax;
+        bad = !open_header<D>(st, cfg, count) || m0 >= count ||
+              !walk_chain<D>(st, w.len, count, w.lane, my, [&](uint32_t bo, uint32_t &n) -> uint32_t {
+                  if (bo + 8 > w.len) return 0;
+                  const uint64_t n64 = st.u64(bo);
+                  if (n64 > lim) return 0;
+                  n = (uint32_t)n64;
+                  const uint32_t end = bo + 8 + n * kReqBytes;
+                  return end > w.len ? 0 : end;
+              });
+    }
+    const uint32_t rq_in = wave_incl_sum(my.n, w.lane), pp_in = wave_incl_sum(my.np, w.lane);
+    const uint32_t tot_pp = __shfl(pp_in, 63, 64);
+    tot_rq = __shfl(rq_in, 63, 64);
+    t.rq[w.wave][w.lane] = rq_in - my.n;
+    t.pp[w.wave][w.lane] = pp_in - my.np;
+    t.mo[w.wave][w.lane] = (uint16_t)my.off;
+    t.p2[w.wave][w.lane] = (uint16_t)my.bo;
+    __syncthreads();
+    bool wrong = false;
+    if (parse && !bad)
+        wrong = parts_wrong<D>(st, t.pp[w.wave], t.mo[w.wave], tot_pp, cfg.part_cnt, w.lane) |
+                requests_wrong(st, t.rq[w.wave], t.p2[w.wave], tot_rq, cfg.synth_table_size, w.lane);
+    return bad || __any(wrong);
+}
+
+// ---- per batch and per txn
+// what the check keeps of batch w.b: the offsets of a good batch's messages,
+// its counts (a bad one counts nothing) and the first bad batch
+template <class D>
+__device__ __forceinline__ void keep_batch(const WireWs &ws, const WaveBatch &w, bool bad, uint32_t count,
+                                           uint32_t my_off, uint32_t txns, uint32_t accs, uint32_t longest) {
+    if (!bad && w.lane < count) ws.moff[(uint64_t)w.b * D::kStride + w.lane] = (uint16_t)my_off;
+    if (w.lane == 0) {
+        ws.bt[w.b] = bad ? 0u : txns;
+        ws.ba[w.b] = bad ? 0u : accs;
+        ws.bm[w.b] = bad ? (uint8_t)0 : (uint8_t)longest;
+        if (bad) atomicMin(&ws.first[0], w.b);
+    }
+}
+
+// the call's txns and accesses before batch b (after the scan)
+__device__ __forceinline__ void batch_base(const WireWs &ws, uint32_t b, uint32_t &t0, uint32_t &a0) {
+    t0 = ws.ct[b / kWireChunk] + ws.bt[b];
+    a0 = ws.ca[b / kWireChunk] + ws.ba[b];
+}
+
+// a YCSB query at mo: client_startts, where its request count lies and the count
+template <class D>
+__device__ __forceinline__ void query_fields(const Stage &st, uint32_t mo, uint64_t &cst, uint32_t &p2, uint32_t &n) {
+    cst = st.u64(mo + D::kHdr);
+    p2 = mo + D::kFixed + st.u32(mo + D::kHdr + 8) * 8u;
+    n = st.u32(p2);
+}
+
+// txn t: its boundary and what its reply needs
+template <class Out>
+__device__ __forceinline__ void emit_txn_fields(const Out &out, uint32_t t, uint32_t begin, uint64_t txn_id,
+                                                uint64_t cst, uint32_t src) {
+    out.txn_begin[t] = begin;
+    if (out.txn_id) out.txn_id[t] = txn_id;
+    if (out.client_startts) out.client_startts[t] = cst;
+    if (out.return_node) out.return_node[t] = src;
+}
+
+// WorkerThread::get_next_txn_id for one worker (worker_thread.cpp:453-458)
+__device__ __forceinline__ uint64_t worker_txn_id(const dv_wire_cfg &cfg, uint64_t k) {
+    return cfg.node_id + (uint64_t)cfg.node_cnt * k;
+}
+
+// ---- the plan (one workgroup, every thread; both end in a barrier)
+// The first batch of [0, nb) whose txns or accesses, added to those before it,
+// pass the rooms, nb where none does: the running sums only grow, so it is
+// the first batch of the first chunk that does not fit whole.  s_chunk = nc and
+// s_cut = nb were set in front of a barrier; tot_t / tot_a: the chunks' totals.
+__device__ __forceinline__ uint32_t first_overflow(const WireWs &ws, uint32_t nb, uint32_t nc, uint32_t tot_t,
+                                                   uint32_t tot_a, uint64_t room_t, uint64_t room_a,
+                                                   uint32_t *s_chunk, uint32_t *s_cut) {
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < nc; i += kBlock) {
+        const uint32_t it = i + 1 < nc ? ws.ct[i + 1] : tot_t, ia = i + 1 < nc ? ws.ca[i + 1] : tot_a;
+        if (it > room_t || ia > room_a) atomicMin(s_chunk, i);
+    }
+    __syncthreads();
+    const uint32_t cc = *s_chunk;
+    if (cc < nc) {
+        const uint32_t base = cc * kWireChunk;
+        const uint32_t n = nb - base < kWireChunk ? nb - base : kWireChunk;
+        const uint32_t t0 = ws.ct[cc], a0 = ws.ca[cc];
+        const uint32_t ch_t = (cc + 1 < nc ? ws.ct[cc + 1] : tot_t) - t0, ch_a = (cc + 1 < nc ? ws.ca[cc + 1] : tot_a) - a0;
+        for (uint32_t j = tid; j < n; j += kBlock) {
+            const uint32_t it = t0 + (j + 1 < n ? ws.bt[base + j + 1] : ch_t);
+            const uint32_t ia = a0 + (j + 1 < n ? ws.ba[base + j + 1] : ch_a);
+            if (it > room_t || ia > room_a) atomicMin(s_cut, base + j);
+        }
+    }
+    __syncthreads();
+    return *s_cut;
+}
+
+// the longest txn of batches [0, k) (s_max = 0 was set in front of a barrier)
+__device__ __forceinline__ uint32_t longest_below(const WireWs &ws, uint32_t k, uint32_t *s_max) {
+    const uint32_t full = k / kWireChunk;
+    uint32_t mx = 0;
+    for (uint32_t i = threadIdx.x; i < full; i += kBlock) mx = ws.cm[i] > mx ? ws.cm[i] : mx;
+    for (uint32_t j = full * kWireChunk + threadIdx.x; j < k; j += kBlock) mx = ws.bm[j] > mx ? ws.bm[j] : mx;
+    atomicMax(s_max, mx);
+    __syncthreads();
+    return *s_max;
+}
+
+// batches [0, k) of the call's nb hold this many of what (c, b) count per chunk and batch (tot: all nb)
+__device__ __forceinline__ uint32_t sum_below(const uint32_t *c, const uint32_t *b, uint32_t k, uint32_t nb,
+                                              uint32_t tot) {
+    return k == nb ? tot : c[k / kWireChunk] + b[k];
+}
+
 }  // namespace
 
-// Whatever dv_wire_open refuses makes the batch bad, whole.  Every length is
-// compared as the 64-bit count it is before it is multiplied: a count of
-// 2^61 + 1 fails `n > lim`, it never reaches n * 24.
+// Whatever dv_wire_open refuses makes the batch bad, whole.
 __global__ __launch_bounds__(kBlock) void k_wire_check(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
                                                        uint64_t buf_len, const uint64_t *__restrict__ off,
                                                        uint32_t first, uint32_t nb, WireWs ws) {
     __shared__ uint4 s_img[kWireWave][kStageQ];
-    __shared__ uint32_t s_rq[kWireWave][64], s_pp[kWireWave][64];  // requests / partitions before message m
-    __shared__ uint16_t s_mo[kWireWave][64], s_p2[kWireWave][64];  // message m's offset, its request count's
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < nb;
-    uint64_t o0 = 0;
-    uint32_t len = 0;
-    bool bad = live && !batch_span(off, first + b, buf_len, o0, len);
-    const bool parse = live && !bad;
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (parse) st.sh = stage_batch(buf + o0, len, s_img[wave], lane);
-    __syncthreads();
-    uint32_t count = 0, my_off = 0, my_np = 0, my_n = 0, my_p2 = 0;
-    if (parse) {
-        // create_messages' asserts (message.cpp:39-41), then the chain: every lane walks it
-        count = st.u32(8);
-        bad = st.u32(0) != cfg.node_id || st.u32(4) == cfg.node_id || count == 0 || count > kWireMaxMsg;
-        const uint32_t lim = cfg.max_req && cfg.max_req < kReqMax ? cfg.max_req : kReqMax;
-        uint32_t pos = DV_WIRE_HDR;
-        for (uint32_t m = 0; !bad && m < count; m++) {
-            if (pos + kMsgFixed > len) { bad = true; break; }
-            const uint64_t np = st.u64(pos + kMsgHdr + 8);
-            if (st.u32(pos) != DV_WIRE_CL_QRY || np > DV_TPCC_MAX_PARTS) { bad = true; break; }
-            const uint32_t p2 = pos + kMsgFixed + (uint32_t)np * 8u;
-            if (p2 + 8 > len) { bad = true; break; }
-            const uint64_t n = st.u64(p2);
-            if (n > lim) { bad = true; break; }
-            const uint32_t end = p2 + 8 + (uint32_t)n * kReqBytes;
-            if (end > len) { bad = true; break; }
-            if (lane == m) {
-                my_off = pos;
-                my_np = (uint32_t)np;
-                my_n = (uint32_t)n;
-                my_p2 = p2;
-            }
-            pos = end;
-        }
-        if (!bad && pos != len) bad = true;  // exactly `count` messages fill exactly `len` bytes
-    }
-    // (a bad batch's lanes hold zeros or a part of the chain: its tables are not read)
-    const uint32_t rq_in = wave_incl_sum(my_n, lane), pp_in = wave_incl_sum(my_np, lane);
-    const uint32_t tot_rq = __shfl(rq_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64);
-    uint32_t mx = my_n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = __shfl_xor(mx, o, 64);
-        mx = y > mx ? y : mx;
-    }
-    s_rq[wave][lane] = rq_in - my_n;
-    s_pp[wave][lane] = pp_in - my_np;
-    s_mo[wave][lane] = (uint16_t)my_off;
-    s_p2[wave][lane] = (uint16_t)my_p2;
-    __syncthreads();
-    bool wrong = false;
-    if (parse && !bad) {
-        for (uint32_t q = lane; q < tot_pp; q += 64) {  // every partition named below part_cnt
-            const uint32_t m = last_le64(s_pp[wave], q);
-            wrong |= st.u64(s_mo[wave][m] + kMsgFixed + (q - s_pp[wave][m]) * 8u) >= cfg.part_cnt;
-        }
-        for (uint32_t r = lane; r < tot_rq; r += 64) {  // RD / WR of keys inside the table
-            const uint32_t m = last_le64(s_rq[wave], r);
-            const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
-            wrong |= st.u32(ro) > DV_WR || st.u64(ro + 8) >= cfg.synth_table_size;
-        }
-    }
-    bad = bad || __any(wrong);
-    if (!live) return;
-    if (!bad && lane < count) ws.moff[(uint64_t)b * kWireMaxMsg + lane] = (uint16_t)my_off;
-    if (lane == 0) {
-        ws.bt[b] = bad ? 0u : count;
-        ws.ba[b] = bad ? 0u : tot_rq;
-        ws.bm[b] = bad ? (uint8_t)0 : (uint8_t)mx;
-        if (bad) atomicMin(ws.first_bad, b);
-    }
+    __shared__ YcsbTables s_t;
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    uint32_t count = 0, tot_rq;
+    Msg my{};
+    const bool bad = ycsb_batch_bad<Client>(w, cfg, 0, s_t, count, my, tot_rq);
+    const uint32_t mx = wave_max(my.n);
+    if (!w.live) return;
+    keep_batch<Client>(ws, w, bad, count, my.off, count, tot_rq, mx);
 }
 
 // chunk blockIdx.x: the batches' counts become their prefixes inside the chunk
@@ -188,15 +419,16 @@ __global__ __launch_bounds__(kBlock) void k_wire_scan(WireWs ws, uint32_t nb) {
 }
 
 // One workgroup.  Batches are taken up to the first stopper in batch order: a
-// malformed batch (k_wire_check's first_bad), or the first whose txns or
-// accesses, added to those before it, pass the capacities -- the running
-// sums only grow, so that is the first batch of the first chunk that does not
-// fit whole.  (A bad batch counts nothing: it never is the capacity cut.)
+// malformed batch (k_wire_check's ws.first[0]), or the first that does not fit
+// the capacities (first_overflow; a bad batch counts nothing: it never is the
+// capacity cut).  Of the call's out it takes what it reads: the capacities,
+// the boundaries, the count word -- the same for every dialect's out.
 __global__ __launch_bounds__(kBlock) void k_wire_plan(WireWs ws, uint32_t first, uint32_t nb, uint32_t n_batches,
-                                                      uint32_t nc, dv_wire_dev_out out, uint64_t next_txn) {
+                                                      uint32_t nc, uint32_t max_txn, uint64_t max_acc,
+                                                      uint32_t *__restrict__ txn_begin,
+                                                      uint32_t *__restrict__ n_acc_dev, uint64_t next_txn) {
     __shared__ uint32_t lds4[4], s_chunk, s_cut, s_max;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         s_chunk = nc;
         s_cut = nb;
         s_max = 0;
@@ -204,35 +436,12 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan(WireWs ws, uint32_t first,
     const uint32_t tot_t = block_chunk_scan256(ws.ct, nc, lds4);
     const uint32_t tot_a = block_chunk_scan256(ws.ca, nc, lds4);
     __syncthreads();
-    for (uint32_t i = tid; i < nc; i += kBlock) {
-        const uint32_t it = i + 1 < nc ? ws.ct[i + 1] : tot_t, ia = i + 1 < nc ? ws.ca[i + 1] : tot_a;
-        if (it > out.max_txn || ia > out.max_acc) atomicMin(&s_chunk, i);
-    }
-    __syncthreads();
-    const uint32_t cc = s_chunk;
-    if (cc < nc) {
-        const uint32_t base = cc * kWireChunk;
-        const uint32_t n = nb - base < kWireChunk ? nb - base : kWireChunk;
-        const uint32_t t0 = ws.ct[cc], a0 = ws.ca[cc];
-        const uint32_t ch_t = (cc + 1 < nc ? ws.ct[cc + 1] : tot_t) - t0, ch_a = (cc + 1 < nc ? ws.ca[cc + 1] : tot_a) - a0;
-        for (uint32_t j = tid; j < n; j += kBlock) {
-            const uint32_t it = t0 + (j + 1 < n ? ws.bt[base + j + 1] : ch_t);
-            const uint32_t ia = a0 + (j + 1 < n ? ws.ba[base + j + 1] : ch_a);
-            if (it > out.max_txn || ia > out.max_acc) atomicMin(&s_cut, base + j);
-        }
-    }
-    __syncthreads();
-    const uint32_t cut = s_cut, fb = *ws.first_bad;
+    const uint32_t cut = first_overflow(ws, nb, nc, tot_t, tot_a, max_txn, max_acc, &s_chunk, &s_cut);
+    const uint32_t fb = ws.first[0];
     const uint32_t k = fb < cut ? fb : cut;  // batches taken (<= nb)
-    const uint32_t full = k / kWireChunk;
-    uint32_t mx = 0;
-    for (uint32_t i = tid; i < full; i += kBlock) mx = ws.cm[i] > mx ? ws.cm[i] : mx;
-    for (uint32_t j = full * kWireChunk + tid; j < k; j += kBlock) mx = ws.bm[j] > mx ? ws.bm[j] : mx;
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (tid != 0) return;
-    const uint32_t n_txn = k == nb ? tot_t : ws.ct[full] + ws.bt[k];
-    const uint32_t n_acc = k == nb ? tot_a : ws.ca[full] + ws.ba[k];
+    const uint32_t longest = longest_below(ws, k, &s_max);
+    if (threadIdx.x != 0) return;
+    const uint32_t n_txn = sum_below(ws.ct, ws.bt, k, nb, tot_t), n_acc = sum_below(ws.ca, ws.ba, k, nb, tot_a);
     int32_t status = DV_OK;
     if (fb < nb && fb <= cut) status = DV_ERR_ARG;                // the malformed batch comes first
     else if (cut < nb) status = cut ? DV_WIRE_MORE : DV_ERR_ARG;  // (the first batch: it would never fit)
@@ -241,17 +450,16 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan(WireWs ws, uint32_t first,
     r.status = status;
     r.n_taken = first + k;
     r.n_txn = n_txn;
-    r.max_txn_acc = s_max;
+    r.max_txn_acc = longest;
     r.n_acc = n_acc;
     r.next_txn = next_txn + n_txn;
     *ws.res = r;
-    out.txn_begin[n_txn] = n_acc;  // (n_txn <= max_txn)
-    *out.n_acc_dev = n_acc;
+    txn_begin[n_txn] = n_acc;  // (n_txn <= max_txn)
+    *n_acc_dev = n_acc;
 }
 
 // the taken batches (below the plan's n_taken), a wave each: lane m message
-// m's boundary and reply fields, then all lanes the batch's requests in
-// order -- consecutive lanes, consecutive accesses
+// m's boundary and reply fields, then all lanes the batch's requests
 __global__ __launch_bounds__(kBlock) void k_wire_emit(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
                                                       const uint64_t *__restrict__ off, uint32_t first,
                                                       dv_wire_dev_out out, uint64_t next_txn, WireWs ws) {
@@ -260,102 +468,51 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit(dv_wire_cfg cfg, const uin
     __shared__ uint16_t s_p2[kWireWave][64];
     const uint32_t taken = ws.res->n_taken - first;
     if (blockIdx.x * kWireWave >= taken) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < taken;  // (checked by k_wire_check: its span and every field are good)
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (live) {
-        const uint64_t o0 = off[first + b];
-        st.sh = stage_batch(buf + o0, (uint32_t)(off[first + b + 1] - o0), s_img[wave], lane);
-    }
-    __syncthreads();
+    const WaveBatch w = stage_taken_batch(s_img, buf, off, first, taken);
+    const uint32_t lane = w.lane, wave = w.wave;
     uint32_t count = 0, src = 0, my_n = 0, my_p2 = 0, t0 = 0, a0 = 0;
     uint64_t cst = 0;
-    if (live) {
-        src = st.u32(4);
-        count = st.u32(8);
-        t0 = ws.ct[b / kWireChunk] + ws.bt[b];
-        a0 = ws.ca[b / kWireChunk] + ws.ba[b];
-        if (lane < count) {
-            const uint32_t mo = ws.moff[(uint64_t)b * kWireMaxMsg + lane];
-            cst = st.u64(mo + kMsgHdr);
-            my_p2 = mo + kMsgFixed + st.u32(mo + kMsgHdr + 8) * 8u;
-            my_n = st.u32(my_p2);
-        }
+    if (w.live) {
+        src = w.st.u32(4);
+        count = w.st.u32(8);
+        batch_base(ws, w.b, t0, a0);
+        if (lane < count) query_fields<Client>(w.st, ws.moff[(uint64_t)w.b * Client::kStride + lane], cst, my_p2, my_n);
     }
     const uint32_t rq_in = wave_incl_sum(my_n, lane);
     const uint32_t tot_rq = __shfl(rq_in, 63, 64);
     s_rq[wave][lane] = rq_in - my_n;
     s_p2[wave][lane] = (uint16_t)my_p2;
     __syncthreads();
-    if (!live) return;
-    if (lane < count) {
-        const uint32_t t = t0 + lane;
-        out.txn_begin[t] = a0 + rq_in - my_n;
-        // WorkerThread::get_next_txn_id for one worker (worker_thread.cpp:453-458)
-        if (out.txn_id) out.txn_id[t] = cfg.node_id + (uint64_t)cfg.node_cnt * (next_txn + t);
-        if (out.client_startts) out.client_startts[t] = cst;
-        if (out.return_node) out.return_node[t] = src;
-    }
-    for (uint32_t r = lane; r < tot_rq; r += 64) {
-        const uint32_t m = last_le64(s_rq[wave], r);
-        const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
-        const uint32_t acctype = st.u32(ro);
-        const uint64_t key = st.u64(ro + 8);
-        const uint32_t a = a0 + r;
-        if (out.recs32) out.recs32[a] = (uint32_t)key | (acctype == DV_WR ? AR_WR : 0u);
-        if (out.keys) {
-            out.keys[a] = key;
-            out.types[a] = (uint8_t)acctype;
-            out.acc_txn[a] = t0 + m;
-        }
-        if (out.owner) out.owner[a] = (uint8_t)(key % cfg.part_cnt);  // key_to_part
-    }
+    if (!w.live) return;
+    if (lane < count)
+        emit_txn_fields(out, t0 + lane, a0 + rq_in - my_n, worker_txn_id(cfg, next_txn + t0 + lane), cst, src);
+    emit_requests(w.st, s_rq[wave], s_p2[wave], tot_rq, t0, a0, out, cfg.part_cnt, lane,
+                  [](uint32_t m) { return m; });
 }
 
-uint64_t wire_ws_bytes(uint32_t nb) {
-    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
-    // (every array's size a multiple of 8 bytes: moff first, the words, the bytes last)
-    return n * kWireMaxMsg * 2 + 2 * ((n + 1) & ~1ull) * 4 + 3 * ((nc + 1) & ~1ull) * 4 + 8 +
-           sizeof(dv_wire_dev_result) + ((n + 7) & ~7ull);
-}
-
-WireWs wire_ws_carve(void *base, uint32_t nb) {
-    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
-    const uint64_t n2 = (n + 1) & ~1ull, nc2 = (nc + 1) & ~1ull;
-    WireWs w;
-    char *p = static_cast<char *>(base);
-    w.res = reinterpret_cast<dv_wire_dev_result *>(p);
-    p += sizeof(dv_wire_dev_result);
-    w.first_bad = reinterpret_cast<uint32_t *>(p);
-    p += 8;
-    w.moff = reinterpret_cast<uint16_t *>(p);
-    p += n * kWireMaxMsg * 2;
-    w.bt = reinterpret_cast<uint32_t *>(p);
-    p += n2 * 4;
-    w.ba = reinterpret_cast<uint32_t *>(p);
-    p += n2 * 4;
-    w.ct = reinterpret_cast<uint32_t *>(p);
-    p += nc2 * 4;
-    w.ca = reinterpret_cast<uint32_t *>(p);
-    p += nc2 * 4;
-    w.cm = reinterpret_cast<uint32_t *>(p);
-    p += nc2 * 4;
-    w.bm = reinterpret_cast<uint8_t *>(p);
-    return w;
+// the check, the scan and the plan of a client dialect's batches, `check` launched with the kernel's own arguments
+template <class Check>
+static void launch_client_plan(hipStream_t s, uint32_t first, uint32_t nb, uint32_t n_batches, uint32_t max_txn,
+                               uint64_t max_acc, uint32_t *txn_begin, uint32_t *n_acc_dev, uint64_t next_txn,
+                               const WireWs &ws, Check check) {
+    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
+    (void)hipMemsetAsync(ws.first, 0xFF, 2 * sizeof(uint32_t), s);  // kNoBatch
+    static_assert(kNoBatch == 0xFFFFFFFFu, "the memset's value");
+    if (nb) {
+        check((nb + kWireWave - 1) / kWireWave);
+        DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
+    }
+    DV_LAUNCH(k_wire_plan, 1, kBlock, 0, s, ws, first, nb, n_batches, nc, max_txn, max_acc, txn_begin, n_acc_dev,
+              next_txn);
 }
 
 void launch_wire_plan(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
                       const uint64_t *off, uint32_t first, uint32_t nb, uint32_t n_batches,
                       const dv_wire_dev_out &out, uint64_t next_txn, const WireWs &ws) {
-    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
-    (void)hipMemsetAsync(ws.first_bad, 0xFF, sizeof(uint32_t), s);  // kNoBatch
-    static_assert(kNoBatch == 0xFFFFFFFFu, "the memset's value");
-    if (nb) {
-        DV_LAUNCH(k_wire_check, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, buf_len, off, first, nb, ws);
-        DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
-    }
-    DV_LAUNCH(k_wire_plan, 1, kBlock, 0, s, ws, first, nb, n_batches, nc, out, next_txn);
+    launch_client_plan(s, first, nb, n_batches, out.max_txn, out.max_acc, out.txn_begin, out.n_acc_dev, next_txn, ws,
+                       [&](uint32_t grid) {
+                           DV_LAUNCH(k_wire_check, grid, kBlock, 0, s, cfg, buf, buf_len, off, first, nb, ws);
+                       });
 }
 
 void launch_wire_emit(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
@@ -367,9 +524,9 @@ void launch_wire_emit(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf,
 
 // ---- TPC-C client batches (dv_wire_ingest_device_tpcc): the same four
 // launches, k_wire_scan and k_wire_plan as they are.  A TPCCClientQueryMessage
-// is 199 + 8 np + 24 n bytes (kMsgFixed, the partitions, kTpccBody up to the
-// item count, the items, kTpccTail) and expands -- dv_tpcc_expand's lists, a
-// closed form of the message's fields per access -- to 3 accesses (Payment)
+// is 199 + 8 np + 24 n bytes (Client::kFixed, the partitions, kTpccBody up to
+// the item count, the items, kTpccTail) and expands -- dv_tpcc_expand's lists,
+// a closed form of the message's fields per access -- to 3 accesses (Payment)
 // or 3 + 2 ol_cnt (NewOrder).  The knobs the lists follow come by value.
 namespace {
 
@@ -415,85 +572,60 @@ __global__ __launch_bounds__(kBlock) void k_wire_check_tpcc(dv_wire_cfg cfg, dv_
     __shared__ uint4 s_img[kWireWave][kStageQ];
     __shared__ uint32_t s_it[kWireWave][64], s_pp[kWireWave][64];  // items to check / partitions before message m
     __shared__ uint16_t s_mo[kWireWave][64], s_io[kWireWave][64];  // message m's offset, its first item's
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < nb;
-    uint64_t o0 = 0;
-    uint32_t len = 0;
-    bool bad = live && !batch_span(off, first + b, buf_len, o0, len);
-    const bool parse = live && !bad;
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (parse) st.sh = stage_batch(buf + o0, len, s_img[wave], lane);
-    __syncthreads();
-    uint32_t count = 0, my_off = 0, my_np = 0, my_n = 0, my_bo = 0;
-    if (parse) {
-        count = st.u32(8);
-        bad = st.u32(0) != cfg.node_id || st.u32(4) == cfg.node_id || count == 0 || count > kWireMaxMsg;
-        uint32_t pos = DV_WIRE_HDR;
-        for (uint32_t m = 0; !bad && m < count; m++) {
-            if (pos + kMsgFixed > len) { bad = true; break; }
-            const uint64_t np = st.u64(pos + kMsgHdr + 8);
-            if (st.u32(pos) != DV_WIRE_CL_QRY || np > DV_TPCC_MAX_PARTS) { bad = true; break; }
-            const uint32_t bo = pos + kMsgFixed + (uint32_t)np * 8u;
-            if (bo + kTpccBody > len) { bad = true; break; }
-            const uint64_t n = st.u64(bo + kTpccN);
-            if (n > DV_TPCC_MAX_OL) { bad = true; break; }
-            const uint32_t end = bo + kTpccBody + (uint32_t)n * kItemBytes + kTpccTail;
-            if (end > len) { bad = true; break; }
-            if (lane == m) {
-                my_off = pos;
-                my_np = (uint32_t)np;
-                my_n = (uint32_t)n;
-                my_bo = bo;
-            }
-            pos = end;
-        }
-        if (!bad && pos != len) bad = true;  // exactly `count` messages fill exactly `len` bytes
-    }
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane, wave = w.wave;
+    const bool parse = w.live && !w.bad;
+    bool bad = w.bad;
+    uint32_t count = 0;
+    Msg my{};
+    if (parse)
+        bad = !open_header<Client>(st, cfg, count) ||
+              !walk_chain<Client>(st, w.len, count, lane, my, [&](uint32_t bo, uint32_t &n) -> uint32_t {
+                  if (bo + kTpccBody > w.len) return 0;
+                  const uint64_t n64 = st.u64(bo + kTpccN);
+                  if (n64 > DV_TPCC_MAX_OL) return 0;
+                  n = (uint32_t)n64;
+                  const uint32_t end = bo + kTpccBody + n * kItemBytes + kTpccTail;
+                  return end > w.len ? 0 : end;
+              });
     // message m's fixed fields (a Payment's items are skipped unchecked)
     bool wrong = false;
     uint32_t my_acc = 0, my_it = 0;
     if (parse && !bad && lane < count) {
-        const uint64_t tt = st.u64(my_bo), w = st.u64(my_bo + 8), d = st.u64(my_bo + 16), c = st.u64(my_bo + 24);
-        wrong = !in_1_to(w, tp.num_wh) || !in_1_to(d, tp.dist_per_wh);
+        const uint32_t bo = my.bo;
+        const uint64_t tt = st.u64(bo), wh = st.u64(bo + 8), d = st.u64(bo + 16), c = st.u64(bo + 24);
+        wrong = !in_1_to(wh, tp.num_wh) || !in_1_to(d, tp.dist_per_wh);
         if (tt == 1) {
-            wrong |= !in_1_to(st.u64(my_bo + 40), tp.num_wh) || !in_1_to(st.u64(my_bo + 48), tp.dist_per_wh) ||
-                     st.u64(my_bo + kTpccAmount) > kOperandMax;
-            if ((st.u32(my_bo + kTpccByName) & 0xFFu) != 0)
-                wrong |= !has_nul(st.u64(my_bo + kTpccLast)) && !has_nul(st.u64(my_bo + kTpccLast + 8));
+            wrong |= !in_1_to(st.u64(bo + 40), tp.num_wh) || !in_1_to(st.u64(bo + 48), tp.dist_per_wh) ||
+                     st.u64(bo + kTpccAmount) > kOperandMax;
+            if ((st.u32(bo + kTpccByName) & 0xFFu) != 0)
+                wrong |= !has_nul(st.u64(bo + kTpccLast)) && !has_nul(st.u64(bo + kTpccLast + 8));
             else
                 wrong |= !in_1_to(c, tp.cust_per_dist);
             my_acc = 3;
         } else if (tt == 2) {
             // the txn manager walks items[0 .. ol_cnt): the list must hold them, one at least
-            const uint64_t ol_cnt = st.u64(my_bo + kTpccBody + my_n * kItemBytes + 2);
-            wrong |= ol_cnt != my_n || my_n == 0 || !in_1_to(c, tp.cust_per_dist);
-            my_acc = 3 + 2 * my_n;
-            my_it = my_n;
+            const uint64_t ol_cnt = st.u64(bo + kTpccBody + my.n * kItemBytes + 2);
+            wrong |= ol_cnt != my.n || my.n == 0 || !in_1_to(c, tp.cust_per_dist);
+            my_acc = 3 + 2 * my.n;
+            my_it = my.n;
         } else {
             wrong = true;
         }
     }
     // (a bad batch's lanes hold zeros or a part of the chain: its tables are not read)
-    const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my_np, lane);
+    const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my.np, lane);
     const uint32_t ac_in = wave_incl_sum(my_acc, lane);
     const uint32_t tot_it = __shfl(it_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64), tot_ac = __shfl(ac_in, 63, 64);
-    uint32_t mx = my_acc;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = __shfl_xor(mx, o, 64);
-        mx = y > mx ? y : mx;
-    }
+    const uint32_t mx = wave_max(my_acc);  // (at most 3 + 2 * 62)
     s_it[wave][lane] = it_in - my_it;
-    s_pp[wave][lane] = pp_in - my_np;
-    s_mo[wave][lane] = (uint16_t)my_off;
-    s_io[wave][lane] = (uint16_t)(my_bo + kTpccBody);
+    s_pp[wave][lane] = pp_in - my.np;
+    s_mo[wave][lane] = (uint16_t)my.off;
+    s_io[wave][lane] = (uint16_t)(my.bo + kTpccBody);
     __syncthreads();
     if (parse && !bad) {
-        for (uint32_t q = lane; q < tot_pp; q += 64) {  // every partition named below part_cnt
-            const uint32_t m = last_le64(s_pp[wave], q);
-            wrong |= st.u64(s_mo[wave][m] + kMsgFixed + (q - s_pp[wave][m]) * 8u) >= cfg.part_cnt;
-        }
+        wrong |= parts_wrong<Client>(st, s_pp[wave], s_mo[wave], tot_pp, cfg.part_cnt, lane);
         for (uint32_t q = lane; q < tot_it; q += 64) {  // items inside the tables, operands of 56 bits
             const uint32_t m = last_le64(s_it[wave], q);
             const uint32_t io = s_io[wave][m] + (q - s_it[wave][m]) * kItemBytes;
@@ -502,14 +634,8 @@ __global__ __launch_bounds__(kBlock) void k_wire_check_tpcc(dv_wire_cfg cfg, dv_
         }
     }
     bad = bad || __any(wrong);
-    if (!live) return;
-    if (!bad && lane < count) ws.moff[(uint64_t)b * kWireMaxMsg + lane] = (uint16_t)my_off;
-    if (lane == 0) {
-        ws.bt[b] = bad ? 0u : count;
-        ws.ba[b] = bad ? 0u : tot_ac;
-        ws.bm[b] = bad ? (uint8_t)0 : (uint8_t)mx;  // (at most 3 + 2 * 62)
-        if (bad) atomicMin(ws.first_bad, b);
-    }
+    if (!w.live) return;
+    keep_batch<Client>(ws, w, bad, count, my.off, count, tot_ac, mx);
 }
 
 // the taken batches, a wave each: lane m message m's boundary, txn type, reply
@@ -527,26 +653,19 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_t
     __shared__ uint32_t s_mt[kWireWave][64];  // Payment | by name << 1 | w_id's partition << 8 | c_w_id's << 16
     const uint32_t taken = ws.res->n_taken - first;
     if (blockIdx.x * kWireWave >= taken) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < taken;  // (checked by k_wire_check_tpcc: its span and every field are good)
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (live) {
-        const uint64_t o0 = off[first + b];
-        st.sh = stage_batch(buf + o0, (uint32_t)(off[first + b + 1] - o0), s_img[wave], lane);
-    }
-    __syncthreads();
+    const WaveBatch wb = stage_taken_batch(s_img, buf, off, first, taken);
+    const Stage &st = wb.st;
+    const uint32_t lane = wb.lane, wave = wb.wave;
     uint32_t count = 0, src = 0, my_acc = 0, my_io = 0, my_tt = 0, my_mt = 0, t0 = 0, a0 = 0;
     uint64_t cst = 0, k0 = 0, k1 = 0, k2 = 0, h = 0;
-    if (live) {
+    if (wb.live) {
         src = st.u32(4);
         count = st.u32(8);
-        t0 = ws.ct[b / kWireChunk] + ws.bt[b];
-        a0 = ws.ca[b / kWireChunk] + ws.ba[b];
+        batch_base(ws, wb.b, t0, a0);
         if (lane < count) {
-            const uint32_t mo = ws.moff[(uint64_t)b * kWireMaxMsg + lane];
-            cst = st.u64(mo + kMsgHdr);
-            const uint32_t bo = mo + kMsgFixed + st.u32(mo + kMsgHdr + 8) * 8u;
+            const uint32_t mo = ws.moff[(uint64_t)wb.b * Client::kStride + lane];
+            cst = st.u64(mo + Client::kHdr);
+            const uint32_t bo = mo + Client::kFixed + st.u32(mo + Client::kHdr + 8) * 8u;
             my_io = bo + kTpccBody;
             my_tt = st.u32(bo);
             // (validated: every id below its 32-bit bound)
@@ -582,15 +701,11 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_t
     s_hk[wave][lane][1] = k1;
     s_hk[wave][lane][2] = k2;
     __syncthreads();
-    if (!live) return;
+    if (!wb.live) return;
     if (lane < count) {
         const uint32_t t = t0 + lane;
-        out.txn_begin[t] = a0 + ac_in - my_acc;
         if (out.txn_type) out.txn_type[t] = (uint8_t)my_tt;
-        // WorkerThread::get_next_txn_id for one worker (worker_thread.cpp:453-458)
-        if (out.txn_id) out.txn_id[t] = cfg.node_id + (uint64_t)cfg.node_cnt * (next_txn + t);
-        if (out.client_startts) out.client_startts[t] = cst;
-        if (out.return_node) out.return_node[t] = src;
+        emit_txn_fields(out, t, a0 + ac_in - my_acc, worker_txn_id(cfg, next_txn + t), cst, src);
     }
     for (uint32_t r = lane; r < tot_ac; r += 64) {
         const uint32_t m = last_le64(s_ac[wave], r);
@@ -638,50 +753,41 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_t
     }
 }
 
+// cfg as the TPC-C kernels get it: tpcc is a host pointer, the knobs go by value
+static dv_wire_cfg without_tpcc(dv_wire_cfg cfg) {
+    cfg.tpcc = nullptr;
+    return cfg;
+}
+
 void launch_wire_plan_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
                            uint64_t buf_len, const uint64_t *off, uint32_t first, uint32_t nb, uint32_t n_batches,
                            const dv_wire_tpcc_dev_out &out, uint64_t next_txn, const WireWs &ws) {
-    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
-    dv_wire_cfg dc = cfg;
-    dc.tpcc = nullptr;  // (a host pointer: the kernels get the knobs by value)
-    dv_wire_dev_out pl{};  // what k_wire_plan reads of its out: the capacities, the boundaries, the count word
-    pl.max_txn = out.max_txn;
-    pl.max_acc = out.max_acc;
-    pl.txn_begin = out.txn_begin;
-    pl.n_acc_dev = out.n_acc_dev;
-    (void)hipMemsetAsync(ws.first_bad, 0xFF, sizeof(uint32_t), s);  // kNoBatch
-    if (nb) {
-        DV_LAUNCH(k_wire_check_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, dc, tp, buf, buf_len, off, first, nb,
-                  ws);
-        DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
-    }
-    DV_LAUNCH(k_wire_plan, 1, kBlock, 0, s, ws, first, nb, n_batches, nc, pl, next_txn);
+    launch_client_plan(s, first, nb, n_batches, out.max_txn, out.max_acc, out.txn_begin, out.n_acc_dev, next_txn, ws,
+                       [&](uint32_t grid) {
+                           DV_LAUNCH(k_wire_check_tpcc, grid, kBlock, 0, s, without_tpcc(cfg), tp, buf, buf_len, off,
+                                     first, nb, ws);
+                       });
 }
 
 void launch_wire_emit_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
                            const uint64_t *off, uint32_t first, uint32_t nb, const dv_wire_tpcc_dev_out &out,
                            uint64_t next_txn, const WireWs &ws) {
     if (!nb) return;
-    dv_wire_cfg dc = cfg;
-    dc.tpcc = nullptr;
-    DV_LAUNCH(k_wire_emit_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, dc, tp, buf, off, first, out, next_txn,
-              ws);
+    DV_LAUNCH(k_wire_emit_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, without_tpcc(cfg), tp, buf, off, first,
+              out, next_txn, ws);
 }
 
 // ---- CALVIN sequencer streams (dv_wire_ingest_device_calvin): the same four
-// launches with kernels of their own.  The header carries batch_id (84 bytes),
-// an RDONE is the header alone, and the stream is cut at a message: an mbuf's
-// run is its messages from the cursor that name the epoch's batch E, and an
-// epoch ends inside the first mbuf whose run does not reach its end.  The
-// check cannot know E (it may be the first mbuf's own), so it measures every
-// mbuf's run against the id of its own first message; the scan, which knows
-// E, drops the mbufs that lead with another id and finds the first cut.
+// launches, kernels of the same shape over the Calvin dialect.  The header
+// carries batch_id (84 bytes), an RDONE is the header alone, and the stream is
+// cut at a message: an mbuf's run is its messages from the cursor that name
+// the epoch's batch E, and an epoch ends inside the first mbuf whose run does
+// not reach its end.  The check cannot know E (it may be the first mbuf's
+// own), so it measures every mbuf's run against the id of its own first
+// message; the scan, which knows E, drops the mbufs that lead with another id
+// and finds the first cut.
 namespace {
 
-constexpr uint32_t kCalHdr = 84;     // rtype, txn_id, batch_id, mq_time, 7 latencies (Message::mget_size, CALVIN)
-constexpr uint32_t kCalFixed = 100;  // ... client_startts, the partition count
-constexpr uint32_t kCalTxnId = 4, kCalBatchId = 12;  // header offsets
-constexpr uint64_t kNoBatchId = ~0ull;
 constexpr uint32_t kRunLater = 1, kRunEarlier = 2;  // WireCalvinWs::bflag
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {
@@ -690,120 +796,43 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {
 
 }  // namespace
 
-// Whatever dv_wire_open refuses under a CALVIN cfg makes the mbuf bad, whole
-// (every length compared as the 64-bit count it is, as k_wire_check does), and
-// so does a cursor at or past its count.  Lane m keeps message m's rtype and
-// batch id: the run is the lanes from the cursor up to the first whose id
+// Whatever dv_wire_open refuses under a CALVIN cfg makes the mbuf bad, whole,
+// and so does a cursor at or past its count.  Lane m keeps message m's rtype
+// and batch id: the run is the lanes from the cursor up to the first whose id
 // differs from the cursor's.
 __global__ __launch_bounds__(kBlock) void k_wire_check_calvin(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
                                                               uint64_t buf_len, const uint64_t *__restrict__ off,
                                                               uint32_t first, uint32_t msg0, uint32_t nb,
                                                               WireCalvinWs ws) {
     __shared__ uint4 s_img[kWireWave][kStageQ];
-    __shared__ uint32_t s_rq[kWireWave][64], s_pp[kWireWave][64];  // requests / partitions before message m
-    __shared__ uint16_t s_mo[kWireWave][64], s_p2[kWireWave][64];  // message m's offset, its request count's
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < nb;
-    uint64_t o0 = 0;
-    uint32_t len = 0;
-    bool bad = live && !batch_span(off, first + b, buf_len, o0, len);
-    const bool parse = live && !bad;
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (parse) st.sh = stage_batch(buf + o0, len, s_img[wave], lane);
-    __syncthreads();
+    __shared__ YcsbTables s_t;
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    const uint32_t lane = w.lane, b = w.b;
     const uint32_t m0 = b == 0 ? msg0 : 0;  // the cursor's message (the window's first mbuf is the cursor's)
-    uint32_t count = 0, my_off = 0, my_np = 0, my_n = 0, my_p2 = 0, my_rt = 0;
-    uint64_t my_bid = 0;
-    if (parse) {
-        count = st.u32(8);
-        bad = st.u32(0) != cfg.node_id || st.u32(4) == cfg.node_id || count == 0 || count > kWireCalvinMaxMsg ||
-              m0 >= count;
-        const uint32_t lim = cfg.max_req && cfg.max_req < kReqMax ? cfg.max_req : kReqMax;
-        uint32_t pos = DV_WIRE_HDR;
-        for (uint32_t m = 0; !bad && m < count; m++) {
-            if (pos + kCalHdr > len) { bad = true; break; }
-            const uint32_t rt = st.u32(pos);
-            const uint64_t bid = st.u64(pos + kCalBatchId);
-            if (bid == kNoBatchId) { bad = true; break; }
-            uint32_t end = pos + kCalHdr, np32 = 0, n32 = 0, p2 = 0;
-            if (rt == DV_WIRE_CL_QRY) {
-                if (pos + kCalFixed > len) { bad = true; break; }
-                const uint64_t np = st.u64(pos + kCalHdr + 8);
-                if (np > DV_TPCC_MAX_PARTS) { bad = true; break; }
-                p2 = pos + kCalFixed + (uint32_t)np * 8u;
-                if (p2 + 8 > len) { bad = true; break; }
-                const uint64_t n = st.u64(p2);
-                if (n > lim) { bad = true; break; }
-                end = p2 + 8 + (uint32_t)n * kReqBytes;
-                if (end > len) { bad = true; break; }
-                np32 = (uint32_t)np;
-                n32 = (uint32_t)n;
-            } else if (rt != DV_WIRE_RDONE) {
-                bad = true;
-                break;
-            }
-            if (lane == m) {
-                my_off = pos;
-                my_np = np32;
-                my_n = n32;
-                my_p2 = p2;
-                my_rt = rt;
-                my_bid = bid;
-            }
-            pos = end;
-        }
-        if (!bad && pos != len) bad = true;  // exactly `count` messages fill exactly `len` bytes
-    }
-    // (a bad mbuf's lanes hold zeros or a part of the chain: its tables are not read)
-    const uint32_t rq_in = wave_incl_sum(my_n, lane), pp_in = wave_incl_sum(my_np, lane);
-    const uint32_t tot_rq = __shfl(rq_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64);
-    s_rq[wave][lane] = rq_in - my_n;
-    s_pp[wave][lane] = pp_in - my_np;
-    s_mo[wave][lane] = (uint16_t)my_off;
-    s_p2[wave][lane] = (uint16_t)my_p2;
-    __syncthreads();
-    bool wrong = false;
-    if (parse && !bad) {  // every message of the mbuf, in the run or not: it is refused whole
-        for (uint32_t q = lane; q < tot_pp; q += 64) {  // every partition named below part_cnt
-            const uint32_t m = last_le64(s_pp[wave], q);
-            wrong |= st.u64(s_mo[wave][m] + kCalFixed + (q - s_pp[wave][m]) * 8u) >= cfg.part_cnt;
-        }
-        for (uint32_t r = lane; r < tot_rq; r += 64) {  // RD / WR of keys inside the table
-            const uint32_t m = last_le64(s_rq[wave], r);
-            const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
-            wrong |= st.u32(ro) > DV_WR || st.u64(ro + 8) >= cfg.synth_table_size;
-        }
-    }
-    bad = bad || __any(wrong);
+    uint32_t count = 0, tot_rq;
+    Msg my{};
+    // every message of the mbuf, in the run or not: it is refused whole
+    const bool bad = ycsb_batch_bad<Calvin>(w, cfg, m0, s_t, count, my, tot_rq);
+    const uint64_t my_bid = !bad && lane < count ? w.st.u64(my.off + kCalBatchId) : 0;
     // the run: lanes [m0, rend), the first lane behind the cursor whose id is not the cursor's
     const uint64_t lead = shfl_u64(my_bid, m0 & 63u);
     const uint64_t differ = __ballot(lane >= m0 && lane < count && my_bid != lead);
     const uint32_t rend = differ ? (uint32_t)__ffsll((long long)differ) - 1u : count;
     const bool in_run = lane >= m0 && lane < rend;
-    const bool is_q = in_run && my_rt == DV_WIRE_CL_QRY;
+    const bool is_q = in_run && my.rt == DV_WIRE_CL_QRY;
     const uint32_t txns = (uint32_t)__popcll(__ballot(is_q));
-    const uint32_t rdones = (uint32_t)__popcll(__ballot(in_run && my_rt == DV_WIRE_RDONE));
-    const uint32_t run_n = is_q ? my_n : 0u;
+    const uint32_t rdones = (uint32_t)__popcll(__ballot(in_run && my.rt == DV_WIRE_RDONE));
+    const uint32_t run_n = is_q ? my.n : 0u;
     const uint32_t accs = __shfl(wave_incl_sum(run_n, lane), 63, 64);
-    uint32_t mx = run_n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = __shfl_xor(mx, o, 64);
-        mx = y > mx ? y : mx;
-    }
+    const uint32_t mx = wave_max(run_n);
     const uint64_t behind = shfl_u64(my_bid, rend & 63u);
-    if (!live) return;
-    if (!bad && lane < count) ws.moff[(uint64_t)b * kWireCalvinMaxMsg + lane] = (uint16_t)my_off;
+    if (!w.live) return;
+    keep_batch<Calvin>(ws, w, bad, count, my.off, txns, accs, mx);
     if (lane == 0) {
-        ws.bt[b] = bad ? 0u : txns;
-        ws.ba[b] = bad ? 0u : accs;
         ws.br[b] = bad ? 0u : rdones;
-        ws.bm[b] = bad ? (uint8_t)0 : (uint8_t)mx;
         ws.bid[b] = bad ? kNoBatchId : lead;
         ws.brun[b] = bad ? (uint8_t)0 : (uint8_t)(rend - m0);
         ws.bflag[b] = bad || rend >= count ? (uint8_t)0 : (uint8_t)(behind > lead ? kRunLater : kRunEarlier);
-        if (bad) atomicMin(&ws.first[0], b);
     }
 }
 
@@ -854,8 +883,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
                                                              uint32_t nc, dv_wire_dev_out out,
                                                              dv_wire_calvin_pos pos) {
     __shared__ uint32_t lds4[4], s_chunk, s_cut, s_max;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         s_chunk = nc;
         s_cut = nb;
         s_max = 0;
@@ -864,26 +892,10 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
     const uint32_t tot_a = block_chunk_scan256(ws.ca, nc, lds4);
     const uint32_t tot_r = block_chunk_scan256(ws.cr, nc, lds4);
     __syncthreads();
-    const uint64_t room_t = out.max_txn - pos.n_txn, room_a = out.max_acc - pos.n_acc;  // (checked: not negative)
-    for (uint32_t i = tid; i < nc; i += kBlock) {
-        const uint32_t it = i + 1 < nc ? ws.ct[i + 1] : tot_t, ia = i + 1 < nc ? ws.ca[i + 1] : tot_a;
-        if (it > room_t || ia > room_a) atomicMin(&s_chunk, i);
-    }
-    __syncthreads();
-    const uint32_t cc = s_chunk;
-    if (cc < nc) {
-        const uint32_t base = cc * kWireChunk;
-        const uint32_t n = nb - base < kWireChunk ? nb - base : kWireChunk;
-        const uint32_t t0 = ws.ct[cc], a0 = ws.ca[cc];
-        const uint32_t ch_t = (cc + 1 < nc ? ws.ct[cc + 1] : tot_t) - t0, ch_a = (cc + 1 < nc ? ws.ca[cc + 1] : tot_a) - a0;
-        for (uint32_t j = tid; j < n; j += kBlock) {
-            const uint32_t it = t0 + (j + 1 < n ? ws.bt[base + j + 1] : ch_t);
-            const uint32_t ia = a0 + (j + 1 < n ? ws.ba[base + j + 1] : ch_a);
-            if (it > room_t || ia > room_a) atomicMin(&s_cut, base + j);
-        }
-    }
-    __syncthreads();
-    const uint32_t cut = s_cut, fb = nb ? ws.first[0] : kNoBatch, fe = nb ? ws.first[1] : kNoBatch;
+    // (checked: the rooms are not negative)
+    const uint32_t cut = first_overflow(ws, nb, nc, tot_t, tot_a, out.max_txn - pos.n_txn, out.max_acc - pos.n_acc,
+                                        &s_chunk, &s_cut);
+    const uint32_t fb = nb ? ws.first[0] : kNoBatch, fe = nb ? ws.first[1] : kNoBatch;
     uint32_t s = fb < cut ? fb : cut;
     s = fe < s ? fe : s;  // (<= nb)
     uint32_t stop;
@@ -905,24 +917,18 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
     }
     const bool ends = stop == DV_WIRE_STOP_BATCH || stop == DV_WIRE_STOP_STALE;
     const uint32_t k = s + (ends ? 1u : 0u);  // mbufs whose runs are taken (<= nb)
-    const uint32_t full = k / kWireChunk;
-    uint32_t mx = 0;
-    for (uint32_t i = tid; i < full; i += kBlock) mx = ws.cm[i] > mx ? ws.cm[i] : mx;
-    for (uint32_t j = full * kWireChunk + tid; j < k; j += kBlock) mx = ws.bm[j] > mx ? ws.bm[j] : mx;
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (tid != 0) return;
-    const uint32_t n_txn = pos.n_txn + (k == nb ? tot_t : ws.ct[full] + ws.bt[k]);
-    const uint64_t n_acc = pos.n_acc + (k == nb ? tot_a : ws.ca[full] + ws.ba[k]);
-    const uint32_t rdone = pos.rdone + (k == nb ? tot_r : ws.cr[full] + ws.br[k]);
+    const uint32_t longest = longest_below(ws, k, &s_max);
+    if (threadIdx.x != 0) return;
+    const uint32_t n_txn = pos.n_txn + sum_below(ws.ct, ws.bt, k, nb, tot_t);
+    const uint64_t n_acc = pos.n_acc + sum_below(ws.ca, ws.ba, k, nb, tot_a);
     WireCalvinRes r;
     r.pos.batch = stop == DV_WIRE_STOP_END ? n_batches : pos.batch + s;
     r.pos.msg = s == nb ? 0u : m0 + run;
     r.pos.n_txn = n_txn;
-    r.pos.rdone = rdone;
+    r.pos.rdone = pos.rdone + sum_below(ws.cr, ws.br, k, nb, tot_r);
     r.pos.n_acc = n_acc;
     r.pos.batch_id = s > 0 || run > 0 ? E : pos.batch_id;  // (every mbuf taken whole holds a message behind the cursor)
-    r.pos.max_txn_acc = s_max > pos.max_txn_acc ? s_max : pos.max_txn_acc;
+    r.pos.max_txn_acc = longest > pos.max_txn_acc ? longest : pos.max_txn_acc;
     r.pos.stop = stop;
     r.status = stop == DV_WIRE_STOP_END ? DV_OK
                : stop == DV_WIRE_STOP_MALFORMED || stop == DV_WIRE_STOP_STALE ? DV_ERR_ARG
@@ -931,7 +937,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
     r.n_emit = ends && run == 0 ? s : k;  // (an empty run: nothing of mbuf s to decode)
     r.last_end = ends && run > 0 ? m0 + run : kNoBatch;
     r.pad_ = 0;
-    *ws.res = r;
+    *ws.cres = r;
     out.txn_begin[n_txn] = (uint32_t)n_acc;  // (n_txn <= max_txn, n_acc <= max_acc < 2^32)
     if (out.n_acc_dev) *out.n_acc_dev = (uint32_t)n_acc;
 }
@@ -939,8 +945,8 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
 // the window's first n_emit mbufs, a wave each: lane m message m from the
 // cursor (the last mbuf: below the plan's last_end) -- a CL_QRY's txn index a
 // wave prefix over the CL_QRY flags, its boundary and reply fields; then all
-// lanes the requests in order, consecutive lanes, consecutive accesses.
-// Everything lands behind the epoch's n_txn_in txns and n_acc_in accesses.
+// lanes the requests.  Everything lands behind the epoch's n_txn_in txns and
+// n_acc_in accesses.
 __global__ __launch_bounds__(kBlock) void k_wire_emit_calvin(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
                                                              const uint64_t *__restrict__ off, uint32_t first,
                                                              uint32_t msg0, dv_wire_dev_out out, uint32_t n_txn_in,
@@ -948,33 +954,25 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_calvin(dv_wire_cfg cfg, co
     __shared__ uint4 s_img[kWireWave][kStageQ];
     __shared__ uint32_t s_rq[kWireWave][64];
     __shared__ uint16_t s_p2[kWireWave][64], s_tx[kWireWave][64];  // message m's request count's offset, txns before it
-    const uint32_t n_emit = ws.res->n_emit;
+    const uint32_t n_emit = ws.cres->n_emit;
     if (blockIdx.x * kWireWave >= n_emit) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t b = blockIdx.x * kWireWave + wave;
-    const bool live = b < n_emit;  // (checked by k_wire_check_calvin: its span and every field are good)
-    Stage st{reinterpret_cast<const uint32_t *>(s_img[wave]), 0};
-    if (live) {
-        const uint64_t o0 = off[first + b];
-        st.sh = stage_batch(buf + o0, (uint32_t)(off[first + b + 1] - o0), s_img[wave], lane);
-    }
-    __syncthreads();
-    uint32_t src = 0, my_n = 0, my_p2 = 0, my_q = 0, t0 = 0, a0 = 0;
-    uint64_t cst = 0, tid = 0;
-    if (live) {
-        src = st.u32(4);
-        const uint32_t count = st.u32(8), last_end = b + 1 == n_emit ? ws.res->last_end : kNoBatch;
+    const WaveBatch w = stage_taken_batch(s_img, buf, off, first, n_emit);
+    const uint32_t lane = w.lane, wave = w.wave, b = w.b;
+    uint32_t src = 0, my_q = 0, my_n = 0, my_p2 = 0, t0 = 0, a0 = 0;
+    uint64_t tid = 0, cst = 0;
+    if (w.live) {
+        src = w.st.u32(4);
+        const uint32_t count = w.st.u32(8), last_end = b + 1 == n_emit ? ws.cres->last_end : kNoBatch;
         const uint32_t m0 = b == 0 ? msg0 : 0, mend = last_end < count ? last_end : count;
-        t0 = n_txn_in + ws.ct[b / kWireChunk] + ws.bt[b];
-        a0 = n_acc_in + ws.ca[b / kWireChunk] + ws.ba[b];
+        batch_base(ws, b, t0, a0);
+        t0 += n_txn_in;
+        a0 += n_acc_in;
         if (lane >= m0 && lane < mend) {
-            const uint32_t mo = ws.moff[(uint64_t)b * kWireCalvinMaxMsg + lane];
-            if (st.u32(mo) == DV_WIRE_CL_QRY) {
+            const uint32_t mo = ws.moff[(uint64_t)b * Calvin::kStride + lane];
+            if (w.st.u32(mo) == DV_WIRE_CL_QRY) {
                 my_q = 1;
-                tid = st.u64(mo + kCalTxnId);
-                cst = st.u64(mo + kCalHdr);
-                my_p2 = mo + kCalFixed + st.u32(mo + kCalHdr + 8) * 8u;
-                my_n = st.u32(my_p2);
+                tid = w.st.u64(mo + kCalTxnId);  // the sequencer's
+                query_fields<Calvin>(w.st, mo, cst, my_p2, my_n);
             }
         }
     }
@@ -984,64 +982,11 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_calvin(dv_wire_cfg cfg, co
     s_p2[wave][lane] = (uint16_t)my_p2;
     s_tx[wave][lane] = (uint16_t)(q_in - my_q);
     __syncthreads();
-    if (!live) return;
-    if (my_q) {
-        const uint32_t t = t0 + q_in - 1u;
-        out.txn_begin[t] = a0 + rq_in - my_n;
-        if (out.txn_id) out.txn_id[t] = tid;  // the sequencer's
-        if (out.client_startts) out.client_startts[t] = cst;
-        if (out.return_node) out.return_node[t] = src;
-    }
-    for (uint32_t r = lane; r < tot_rq; r += 64) {
-        const uint32_t m = last_le64(s_rq[wave], r);
-        const uint32_t ro = s_p2[wave][m] + 8u + (r - s_rq[wave][m]) * kReqBytes;
-        const uint32_t acctype = st.u32(ro);
-        const uint64_t key = st.u64(ro + 8);
-        const uint32_t a = a0 + r;
-        if (out.recs32) out.recs32[a] = (uint32_t)key | (acctype == DV_WR ? AR_WR : 0u);
-        out.keys[a] = key;
-        out.types[a] = (uint8_t)acctype;
-        out.acc_txn[a] = t0 + s_tx[wave][m];
-        if (out.owner) out.owner[a] = (uint8_t)(key % cfg.part_cnt);  // key_to_part
-    }
-}
-
-uint64_t wire_calvin_ws_bytes(uint32_t nb) {
-    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
-    // (every array's size a multiple of 8 bytes: the ids and moff first, the words, the bytes last)
-    return 64 + 8 + n * 8 + n * kWireCalvinMaxMsg * 2 + 3 * ((n + 1) & ~1ull) * 4 + 4 * ((nc + 1) & ~1ull) * 4 +
-           3 * ((n + 7) & ~7ull);
-}
-
-WireCalvinWs wire_calvin_ws_carve(void *base, uint32_t nb) {
-    const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
-    const uint64_t n2 = (n + 1) & ~1ull, nc2 = (nc + 1) & ~1ull, n8 = (n + 7) & ~7ull;
-    WireCalvinWs w;
-    char *p = static_cast<char *>(base);
-    w.res = reinterpret_cast<WireCalvinRes *>(p);
-    p += 64;
-    w.first = reinterpret_cast<uint32_t *>(p);
-    p += 8;
-    w.bid = reinterpret_cast<uint64_t *>(p);
-    p += n * 8;
-    w.moff = reinterpret_cast<uint16_t *>(p);
-    p += n * kWireCalvinMaxMsg * 2;
-    uint32_t **words[] = {&w.bt, &w.ba, &w.br};
-    for (uint32_t **q : words) {
-        *q = reinterpret_cast<uint32_t *>(p);
-        p += n2 * 4;
-    }
-    uint32_t **chunks[] = {&w.ct, &w.ca, &w.cr, &w.cm};
-    for (uint32_t **q : chunks) {
-        *q = reinterpret_cast<uint32_t *>(p);
-        p += nc2 * 4;
-    }
-    uint8_t **bytes[] = {&w.bm, &w.brun, &w.bflag};
-    for (uint8_t **q : bytes) {
-        *q = reinterpret_cast<uint8_t *>(p);
-        p += n8;
-    }
-    return w;
+    if (!w.live) return;
+    if (my_q) emit_txn_fields(out, t0 + q_in - 1u, a0 + rq_in - my_n, tid, cst, src);
+    const uint16_t *tx = s_tx[wave];
+    emit_requests(w.st, s_rq[wave], s_p2[wave], tot_rq, t0, a0, out, cfg.part_cnt, lane,
+                  [tx](uint32_t m) { return (uint32_t)tx[m]; });
 }
 
 void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,

@@ -36,6 +36,30 @@ class WireEpoch(Epoch):
     rdone: int = 0                     # CALVIN: RDONEs taken for batch_id
 
 
+def _pack_replies(cfg, n, batch_id, txn_id, client_startts, return_node, commit):
+    """The host packer (dv_wire_respond) over n txns' reply fields (host
+    arrays; client_startts None under CALVIN, whose acks carry none) -> the
+    reply batches (bytes) of the txns whose commit byte is set, of every txn
+    when commit is None."""
+    tid, rn = np.ascontiguousarray(txn_id, np.uint64), np.ascontiguousarray(return_node, np.uint32)
+    cst = None if client_startts is None else np.ascontiguousarray(client_startts, np.uint64)
+    e = L.WireEpoch()
+    e.n_txn, e.max_txn = n, n
+    e.batch_id = L.WIRE_NO_BATCH_ID if batch_id is None else batch_id
+    e.txn_id, e.return_node = tid.ctypes.data, rn.ctypes.data
+    e.client_startts = None if cst is None else cst.ctypes.data
+    # a reply: the header (Message::mget_size, message.cpp:196-209), then client_startts or the ack's result;
+    # a batch holds (MSG_MAX - 12) // its size of them; one partial batch per destination
+    msg = 4 + 8 + (8 if cfg.calvin else 0) + 8 + 7 * 8 + (4 if cfg.calvin else 8)
+    max_b = n // ((L.WIRE_MSG_MAX - L.WIRE_HDR) // msg) + len(np.unique(rn)) + 1
+    out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
+    off = np.zeros(max_b + 1, np.uint64)
+    nb = ctypes.c_uint32()
+    L.check(L.lib().dv_wire_respond(ctypes.byref(cfg), ctypes.byref(e), _ptr(commit), _ptr(out), len(out),
+                                    _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
+    return [out[int(off[b]):int(off[b + 1])].tobytes() for b in range(nb.value)]
+
+
 class WireIngress:
     """dv_wire_open / dv_wire_decode / dv_wire_respond over host buffers of
     max_txn txns and max_acc accesses.  feed(batch) decodes a received batch
@@ -130,37 +154,63 @@ class WireIngress:
         """Closes and returns the epoch being filled."""
         return self._close()
 
-    def _hdr(self):  # Message::mget_size (message.cpp:196-209)
-        return 4 + 8 + (8 if self.cfg.calvin else 0) + 8 + 7 * 8
-
     def respond(self, ep, commit=None):
         """The replies to a decoded epoch as a list of batches (bytes):
         CL_RSP for every committed txn (commit bytes), or under CALVIN a
         CALVIN_ACK for every txn."""
         n = ep.n_txn
-        e = L.WireEpoch()
-        e.n_txn, e.max_txn = n, n
-        e.batch_id = (1 << 64) - 1 if ep.batch_id is None else ep.batch_id
-        tid = np.ascontiguousarray(ep.txn_id, np.uint64)
-        cst = np.ascontiguousarray(ep.client_startts, np.uint64)
-        rn = np.ascontiguousarray(ep.return_node, np.uint32)
-        e.txn_id, e.client_startts, e.return_node = tid.ctypes.data, cst.ctypes.data, rn.ctypes.data
         cm = None if commit is None else np.ascontiguousarray(np.asarray(commit)[:n], np.uint8)
-        # (a batch holds (MSG_MAX - 12) // message size replies; one partial batch per destination)
-        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (self._hdr() + (4 if self.cfg.calvin else 8))
-        max_b = n // per + len(np.unique(rn)) + 1
-        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
-        off = np.zeros(max_b + 1, np.uint64)
-        nb = ctypes.c_uint32()
-        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
-                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
-        return [out[int(off[b]):int(off[b + 1])].tobytes() for b in range(nb.value)]
+        return _pack_replies(self.cfg, n, ep.batch_id, ep.txn_id, ep.client_startts, ep.return_node, cm)
 
 
-class _DeviceReplies:
-    """The replies of an epoch ingested on the device, whatever the workload:
-    what DeviceWireIngress and TpccDeviceWireIngress share (engine, cfg, _dev
-    and the three reply tensors txn_id / client_startts / return_node)."""
+class _DeviceIngress:
+    """What the device ingresses share: the engine whose context and stream
+    they work on, the cfg, the capacities, the device (_dev) and the tensors
+    every dialect fills -- txn_begin and the reply fields txn_id /
+    client_startts / return_node."""
+
+    def __init__(self, engine, cfg, max_txn, max_acc, device):
+        import torch
+        self.engine, self.cfg, self._dev = engine, cfg, device
+        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
+        self.txn_begin = self._new(self.max_txn + 1, torch.int32)
+        self.txn_id, self.client_startts = self._new(self.max_txn, torch.int64), self._new(self.max_txn, torch.int64)
+        self.return_node = self._new(self.max_txn, torch.int32)
+
+    def _new(self, n, dtype):
+        import torch
+        return torch.empty(n, dtype=dtype, device=self._dev)
+
+    def _new_accesses(self, *dtypes):
+        """a tensor of max_acc elements (one at least) per dtype"""
+        return [self._new(max(1, self.max_acc), dt) for dt in dtypes]
+
+    @staticmethod
+    def _upload(buf, off, device):
+        """numpy bytes / offsets as the device tensors the entry points take"""
+        import torch
+        if isinstance(buf, np.ndarray):
+            buf = torch.from_numpy(np.ascontiguousarray(buf, np.uint8)).to(device)
+        if isinstance(off, np.ndarray):
+            off = torch.from_numpy(np.ascontiguousarray(off, np.uint64).view(np.int64)).to(device)
+        return buf, off
+
+    @staticmethod
+    def _check(rc, launched, what):
+        """raises unless the kernels ran and decided rc: a call refused before
+        any launch (launched False: its result record untouched) or a HIP failure"""
+        if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or not launched:
+            L.check(rc, what)
+
+    def _with_replies(self, ep, n):
+        """ep with the device reply arrays of its n txns"""
+        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
+        return ep
+
+
+class _DeviceReplies(_DeviceIngress):
+    """The CL_RSP replies of an epoch of client batches ingested on the
+    device, whatever the workload (DeviceWireIngress, TpccDeviceWireIngress)."""
 
     def respond(self, ep, d_commit):
         """The CL_RSP batches (bytes) of the epoch's committed txns (d_commit:
@@ -184,20 +234,9 @@ class _DeviceReplies:
         reply fields, every one committed"""
         if not c:
             return []
-        e = L.WireEpoch()
-        e.n_txn, e.max_txn, e.batch_id = c, c, (1 << 64) - 1
-        h_tid, h_cst, h_rn = tid[:c].cpu().numpy(), cst[:c].cpu().numpy(), rn[:c].cpu().numpy()
-        e.txn_id, e.client_startts, e.return_node = h_tid.ctypes.data, h_cst.ctypes.data, h_rn.ctypes.data
-        cm = np.ones(max(1, c), np.uint8)
-        # (a batch holds (MSG_MAX - 12) // message size replies; one partial batch per destination)
-        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 7 * 8 + 8)
-        max_b = c // per + len(np.unique(h_rn)) + 1
-        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
-        off = np.zeros(max_b + 1, np.uint64)
-        nb = ctypes.c_uint32()
-        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), _ptr(cm), _ptr(out), len(out),
-                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
-        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
+        h = lambda t, dt: t[:c].cpu().numpy().view(dt)  # noqa: E731
+        return _pack_replies(self.cfg, c, None, h(tid, np.uint64), h(cst, np.uint64), h(rn, np.uint32),
+                             np.ones(c, np.uint8))
 
     def respond_logged(self, src):
         """The CL_RSP batches (bytes) of the pool txns `src` names: a slice of
@@ -214,16 +253,6 @@ class _DeviceReplies:
         self.engine._after_torch()
         return self._pack(self.txn_id[idx], self.client_startts[idx], self.return_node[idx], c)
 
-    @staticmethod
-    def _upload(buf, off, device):
-        """numpy bytes / offsets as the device tensors the entry points take"""
-        import torch
-        if isinstance(buf, np.ndarray):
-            buf = torch.from_numpy(np.ascontiguousarray(buf, np.uint8)).to(device)
-        if isinstance(off, np.ndarray):
-            off = torch.from_numpy(np.ascontiguousarray(off, np.uint64).view(np.int64)).to(device)
-        return buf, off
-
 
 class TpccDeviceWireIngress(_DeviceReplies):
     """dv_wire_ingest_device_tpcc over device buffers of max_txn txns and
@@ -236,20 +265,14 @@ class TpccDeviceWireIngress(_DeviceReplies):
 
     def __init__(self, engine, params, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, device="cuda"):
         import torch
-        self.engine = engine
+        super().__init__(engine, L.WireCfg(L.TPCC, 0, node_id, node_cnt, part_cnt, 0, 0, ctypes.pointer(params)),
+                         max_txn, max_acc, device)
         self.params = params
-        self.cfg = L.WireCfg(L.TPCC, 0, node_id, node_cnt, part_cnt, 0, 0, ctypes.pointer(params))
-        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
         self.next_txn = 0
-        A, T = max(1, self.max_acc), self.max_txn
-        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
-        self.txn_begin, self.n_acc_dev = new(T + 1, torch.int32), new(1, torch.int32)
-        self.keys, self.types, self.acc_txn = new(A, torch.int64), new(A, torch.uint8), new(A, torch.int32)
-        self.tables, self.args, self.owner = new(A, torch.uint8), new(A, torch.int64), new(A, torch.uint8)
-        self.txn_type = new(T, torch.uint8)
-        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
-        self.return_node = new(T, torch.int32)
-        self._dev = device
+        self.n_acc_dev = self._new(1, torch.int32)
+        self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
+        self.tables, self.args, self.owner = self._new_accesses(torch.uint8, torch.int64, torch.uint8)
+        self.txn_type = self._new(self.max_txn, torch.uint8)
 
     def feed_buffer(self, buf, off, first_batch=0):
         """Batches first_batch.. of buf (a torch uint8 device tensor, or a numpy
@@ -270,8 +293,7 @@ class TpccDeviceWireIngress(_DeviceReplies):
         rc = L.lib().dv_wire_ingest_device_tpcc(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(), buf.numel(),
                                                 off.data_ptr(), off.numel() - 1, first_batch, ctypes.byref(out),
                                                 self.next_txn, ctypes.byref(res))
-        if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or (rc == L.DV_ERR_ARG and res.status != rc):
-            L.check(rc, "dv_wire_ingest_device_tpcc")  # (refused before any launch, or a HIP failure)
+        self._check(rc, res.status == rc, "dv_wire_ingest_device_tpcc")
         self._held = (buf, off)  # (the decode may still read them when this returns)
         self.next_txn = res.next_txn
         n, a = res.n_txn, res.n_acc
@@ -279,8 +301,7 @@ class TpccDeviceWireIngress(_DeviceReplies):
                                       max_txn_acc=res.max_txn_acc)
         ep.args, ep.owner = self.args[:a], self.owner[:a]
         ep.txn_begin, ep.txn_type = self.txn_begin[:n + 1], self.txn_type[:n]
-        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
-        return ep, res.n_taken, res.status
+        return self._with_replies(ep, n), res.n_taken, res.status
 
 
 class DeviceWireIngress(_DeviceReplies):
@@ -294,27 +315,18 @@ class DeviceWireIngress(_DeviceReplies):
     def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
                  device="cuda"):
         import torch
-        self.engine = engine
-        self.cfg = L.WireCfg(L.YCSB, 0, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
-        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
+        super().__init__(engine, L.WireCfg(L.YCSB, 0, node_id, node_cnt, part_cnt, max_req, synth_table_size, None),
+                         max_txn, max_acc, device)
         self.next_txn = 0
-        A, T = max(1, self.max_acc), self.max_txn
-        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
-        self.txn_begin, self.n_acc_dev = new(T + 1, torch.int32), new(1, torch.int32)
+        self.n_acc_dev = self._new(1, torch.int32)
         # 4-byte records hold keys below 2^31 (dv_epoch_dev::recs32)
-        self.recs32 = new(A, torch.int32) if synth_table_size <= 1 << 31 else None
+        self.recs32 = self._new_accesses(torch.int32)[0] if synth_table_size <= 1 << 31 else None
         self.keys = self.types = self.acc_txn = None  # (allocated by the first epoch that needs them)
-        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
-        self.return_node = new(T, torch.int32)
-        self._dev = device
 
     def _old_form(self):
         import torch
         if self.keys is None:
-            A = max(1, self.max_acc)
-            self.keys = torch.empty(A, dtype=torch.int64, device=self._dev)
-            self.types = torch.empty(A, dtype=torch.uint8, device=self._dev)
-            self.acc_txn = torch.empty(A, dtype=torch.int32, device=self._dev)
+            self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
 
     def _ingest(self, buf, off, first_batch, old):
         out = L.WireDevOut(self.max_txn, 0, self.max_acc, self.txn_begin.data_ptr(), self.n_acc_dev.data_ptr(),
@@ -326,8 +338,7 @@ class DeviceWireIngress(_DeviceReplies):
         rc = L.lib().dv_wire_ingest_device(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(), buf.numel(),
                                            off.data_ptr(), off.numel() - 1, first_batch, ctypes.byref(out),
                                            self.next_txn, ctypes.byref(res))
-        if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or (rc == L.DV_ERR_ARG and res.status != rc):
-            L.check(rc, "dv_wire_ingest_device")  # (refused before any launch, or a HIP failure)
+        self._check(rc, res.status == rc, "dv_wire_ingest_device")
         return res
 
     def feed_buffer(self, buf, off, first_batch=0):
@@ -363,11 +374,10 @@ class DeviceWireIngress(_DeviceReplies):
         else:
             ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n,
                                           max_txn_acc=res.max_txn_acc)
-        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
-        return ep, res.n_taken, res.status
+        return self._with_replies(ep, n), res.n_taken, res.status
 
 
-class CalvinDeviceWireIngress:
+class CalvinDeviceWireIngress(_DeviceIngress):
     """dv_wire_ingest_device_calvin over device buffers of max_txn txns and
     max_acc accesses on `engine`'s context (YCSB under CALVIN): sequencer
     streams, cut at message granularity, appended into one open epoch.  An
@@ -379,16 +389,9 @@ class CalvinDeviceWireIngress:
     def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
                  device="cuda"):
         import torch
-        self.engine = engine
-        self.cfg = L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
-        self.max_txn, self.max_acc = int(max_txn), int(max_acc)
-        A, T = max(1, self.max_acc), self.max_txn
-        new = lambda n, dt: torch.empty(n, dtype=dt, device=device)  # noqa: E731
-        self.txn_begin = new(T + 1, torch.int32)
-        self.keys, self.types, self.acc_txn = new(A, torch.int64), new(A, torch.uint8), new(A, torch.int32)
-        self.txn_id, self.client_startts = new(T, torch.int64), new(T, torch.int64)
-        self.return_node = new(T, torch.int32)
-        self._dev = device
+        super().__init__(engine, L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None),
+                         max_txn, max_acc, device)
+        self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
         self._held = []
         self.status = L.DV_OK
         self._open()
@@ -410,7 +413,7 @@ class CalvinDeviceWireIngress:
         stream got there; CAPACITY: the epoch is full; MALFORMED / STALE: the
         mbuf / message at the cursor is refused).  self.status holds the C
         status.  A window's end (WIRE_STOP_WINDOW) is called again here."""
-        buf, off = _DeviceReplies._upload(buf, off, self._dev)
+        buf, off = self._upload(buf, off, self._dev)
         self.engine._after_torch()
         p = L.WireCalvinPos()
         if pos is not None:
@@ -425,8 +428,7 @@ class CalvinDeviceWireIngress:
             rc = L.lib().dv_wire_ingest_device_calvin(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(),
                                                       buf.numel(), off.data_ptr(), off.numel() - 1,
                                                       ctypes.byref(out), ctypes.byref(p))
-            if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or p.stop == 0xFFFFFFFF:
-                L.check(rc, "dv_wire_ingest_device_calvin")  # (refused before any launch, or a HIP failure)
+            self._check(rc, p.stop != 0xFFFFFFFF, "dv_wire_ingest_device_calvin")
             if p.stop != L.WIRE_STOP_WINDOW:
                 break
         self._held.append((buf, off))  # (the decode may still read them when this returns)
@@ -445,7 +447,7 @@ class CalvinDeviceWireIngress:
                                       max_txn_acc=self.max_txn_acc)
         ep.batch_id, ep.rdone = self.batch_id, self.rdone
         ep.txn_begin = self.txn_begin[:n + 1]
-        ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
+        self._with_replies(ep, n)
         self._held = self._held[-2:]
         self._open()
         return ep
@@ -474,20 +476,8 @@ class CalvinDeviceWireIngress:
         if not n:
             return []
         self.engine._after_torch()
-        e = L.WireEpoch()
-        e.n_txn, e.max_txn = n, n
-        e.batch_id = L.WIRE_NO_BATCH_ID if ep.batch_id is None else ep.batch_id
-        tid, rn = ep.txn_id.cpu().numpy(), ep.return_node.cpu().numpy()
-        e.txn_id, e.return_node = tid.ctypes.data, rn.ctypes.data
-        # (a batch holds (MSG_MAX - 12) // message size acks; one partial batch per destination)
-        per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // (4 + 8 + 8 + 8 + 7 * 8 + 4)
-        max_b = n // per + len(np.unique(rn)) + 1
-        out = np.zeros(max_b * L.WIRE_MSG_MAX, np.uint8)
-        off = np.zeros(max_b + 1, np.uint64)
-        nb = ctypes.c_uint32()
-        L.check(L.lib().dv_wire_respond(ctypes.byref(self.cfg), ctypes.byref(e), None, _ptr(out), len(out),
-                                        _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
-        return [out[int(off[k]):int(off[k + 1])].tobytes() for k in range(nb.value)]
+        return _pack_replies(self.cfg, n, ep.batch_id, ep.txn_id.cpu().numpy().view(np.uint64), None,
+                             ep.return_node.cpu().numpy().view(np.uint32), None)
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

@@ -201,6 +201,11 @@ def good_cases(seed=7, bid=9):
     out.append(("query_then_rdone", mbuf([message(_reqs(rng, 10), [1], bid, 77, 5, rng), rdone(bid, rng)], 6), 1, 10, 1))
     # (what the YCSB entry's cases call malformed and CALVIN does not: an RDONE behind a query)
     out.append(("rtype_rdone", mbuf([message(_reqs(rng, 3), [0], bid, 9, 1, rng), rdone(bid)]), 1, 3, 1))
+    # past lane 64 of the flat loops: 90 partitions in an mbuf, 128 requests in a message; an RDONE behind each
+    p90 = [message([], [i % PART_CNT, 1, 2], bid, 400 + i, 50 + i, rng) for i in range(30)]
+    assert len(mbuf(p90)) == 30 * 132 + 12 == 3972 and len(mbuf(p90 + [rdone(bid, rng)])) <= 4096
+    out.append(("partitions_90", mbuf(p90 + [rdone(bid, rng)], 7), 30, 0, 1))
+    out.append(("requests_128", mbuf([message(_reqs(rng, 128), [0], bid, 500, 90, rng), rdone(bid, rng)], 7), 1, 128, 1))
     return out
 
 
@@ -240,6 +245,14 @@ def malformed_cases(seed=11, bid=9):
     m.append(("requests_wrap_2_61_plus_1", mbuf([q(_reqs(rng, 1), [0], n_reqs=(1 << 61) + 1)]), 0))
     m.append(("partitions_wrap_2_61", mbuf([q(_reqs(rng, 1), [], n_parts=1 << 61)]), 0))
     m.append(("requests_2_32_plus_1", mbuf([q(_reqs(rng, 1), [0], n_reqs=(1 << 32) + 1)]), 0))
+    # the twins of good_cases' partitions_90 / requests_128: the bad field past flat index 63 of its loop
+    parts = [[0, 1, 2] for _ in range(30)]
+    parts[82 // 3][82 % 3] = PART_CNT
+    m.append(("partition_82_of_90_out_of_range", mbuf([q([], p) for p in parts] + [rdone(bid, rng)]), 0))
+    assert len(m[-1][1]) == 3972 + 84
+    reqs = _reqs(rng, 128)
+    reqs[100] = (reqs[100][0], ROWS)
+    m.append(("request_100_of_128_key_is_table_size", mbuf([q(reqs, [0]), rdone(bid, rng)]), 0))
     # CALVIN's own
     m.append(("batch_id_max_on_a_query", mbuf([ok(), message(_reqs(rng, 2), [0], U64, 1, 6, rng)]), 0))
     m.append(("batch_id_max_on_an_rdone", mbuf([ok(), rdone(U64, rng)]), 0))

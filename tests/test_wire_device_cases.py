@@ -77,6 +77,11 @@ def good_cases(seed=7):
                   message([], [], 302, rng)], 8)
     assert len(full) == 4096
     out.append(("full_4096", full, 3, 157))
+    # past lane 64 of the flat loops: 90 partitions in a batch, and (above) 128 requests in a message
+    p90 = batch([message([], [i % PART_CNT, 1, 2], 400 + i, rng) for i in range(30)], 9)
+    assert len(p90) == 30 * 124 + 12 == 3732
+    out.append(("partitions_90", p90, 30, 0))
+    out.append(("requests_128", batch([message(_reqs(rng, 128), [0], 500, rng)], 9), 1, 128))
     return out
 
 
@@ -116,6 +121,14 @@ def malformed_cases(seed=11):
     m.append(("requests_wrap_2_61_plus_1", batch([message(_reqs(rng, 1), [0], 1, rng, n_reqs=(1 << 61) + 1)]), 0))
     m.append(("partitions_wrap_2_61", batch([message(_reqs(rng, 1), [], 1, rng, n_parts=1 << 61)]), 0))
     m.append(("requests_2_32_plus_1", batch([message(_reqs(rng, 1), [0], 1, rng, n_reqs=(1 << 32) + 1)]), 0))
+    # the twins of good_cases' partitions_90 / requests_128: the bad field past flat index 63 of its loop
+    parts = [[0, 1, 2] for _ in range(30)]
+    parts[82 // 3][82 % 3] = PART_CNT
+    m.append(("partition_82_of_90_out_of_range", batch([message([], p, 1, rng) for p in parts]), 0))
+    assert len(m[-1][1]) == 3732
+    reqs = _reqs(rng, 128)
+    reqs[100] = (reqs[100][0], ROWS)
+    m.append(("request_100_of_128_key_is_table_size", batch([message(reqs, [0], 1, rng)]), 0))
     return m
 
 

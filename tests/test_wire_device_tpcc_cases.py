@@ -153,6 +153,13 @@ def good_cases(pset="base", seed=7):
     qs = [pay(1, 1, 1), neworder(_items(rng, 5, p, 1)), pay(1, 2, 0, name=b"PRESEING"), neworder(_items(rng, 15, p, 2)),
           pay(W_, 5, 77, c_w=1, c_d=2)]
     out.append(("mixed", batch([tmsg(q, 900 + i) for i, q in enumerate(qs)], 9), 5, sum(_acc(q) for q in qs)))
+    # past lane 64 of the flat loops: 68 partitions in a batch, 80 items in a batch
+    qs = [pay(1 + i % W_, 1 + i % 10, 1 + i, parts=[i % PART_CNT, 1, 2, 3]) for i in range(17)]
+    out.append(("partitions_68", batch([tmsg(q, 950 + i) for i, q in enumerate(qs)], 9), 17, 51))
+    assert len(out[-1][1]) == 17 * 231 + 12 == 3939
+    qs = [neworder(_items(rng, 40, p, 1)), neworder(_items(rng, 40, p, 2), 2)]
+    out.append(("items_80", batch([tmsg(q, 970 + i) for i, q in enumerate(qs)], 9), 2, 166))
+    assert len(out[-1][1]) == 2 * 1167 + 12 == 2346
     return out
 
 
@@ -222,6 +229,15 @@ def malformed_cases(seed=11):
     m.append(("src_is_this_node", batch(ok(), src=NODE)))
     m.append(("len_above_4096", batch([tmsg(neworder(_items(rng, 62, p, 1))) for _ in range(3)])))
     assert len(m[-1][1]) > 4096
+    # the twins of good_cases' partitions_68 / items_80: the bad field past flat index 63 of its loop
+    parts = [[0, 1, 2, 3] for _ in range(17)]
+    parts[66 // 4][66 % 4] = PART_CNT
+    m.append(("partition_66_of_68_out_of_range", batch([tmsg(pay(1, 1, 1 + i, parts=x)) for i, x in enumerate(parts)])))
+    assert len(m[-1][1]) == 3939
+    m.append(("item_70_of_80_i_id_above_max_items",
+              batch([tmsg(neworder(_items(rng, 40, p, 1))),
+                     tmsg(neworder(_items(rng, 40, p, 1)), item_patch=(70 - 40, 0, p.max_items + 1))])))
+    assert len(m[-1][1]) == 2346
     return m
 
 
