@@ -682,6 +682,25 @@ void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_
 void launch_wire_emit_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
                              uint32_t nb, const dv_wire_dev_out &out, const dv_wire_calvin_pos &pos,
                              const WireCalvinWs &ws);
+// TPC-C under CALVIN (dv_wire_ingest_device_calvin_tpcc): the same two steps,
+// tp by value.  A CL_QRY is 207 + 8 np + 24 n bytes, an RDONE 84: an mbuf's
+// 4,084 message bytes hold at most kWireCalvinMaxMsg messages (RDONEs alone)
+// and at most 19 txns; a message of n items is 207 + 24 n bytes at least for
+// 3 + 2 n accesses at most, 12 bytes an access at least, so an mbuf expands to
+// fewer than kWireTpccBatchAcc accesses, as a client batch does, and the
+// longest txn, 3 + 2 * 62 = 127 accesses, fits the per-mbuf byte (WireWs::bm).
+// A call looks at max(max_txn - n_txn + 1, 256) <= kWireTpccMaxTxn + 1 mbufs:
+// every running sum of k_wire_scan_calvin / k_wire_plan_calvin stays in 32 bits.
+static_assert(((uint64_t)kWireTpccMaxTxn + 1) * kWireCalvinMaxMsg < (1ull << 32),
+              "a call's txns and RDONEs fit 32 bits");
+static_assert(3 + 2 * DV_TPCC_MAX_OL <= 255, "the longest txn fits WireWs::bm");
+void launch_wire_plan_calvin_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                                  uint64_t buf_len, const uint64_t *off, uint32_t nb, uint32_t n_batches,
+                                  const dv_wire_tpcc_dev_out &out, const dv_wire_calvin_pos &pos,
+                                  const WireCalvinWs &ws);
+void launch_wire_emit_calvin_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                                  const uint64_t *off, uint32_t nb, const dv_wire_tpcc_dev_out &out,
+                                  const dv_wire_calvin_pos &pos, const WireCalvinWs &ws);
 // the committed txns' reply fields compacted in txn order; bc: reply_tiles(n_txn) + 1
 // words, bc[reply_tiles(n_txn)] = their count
 uint32_t reply_tiles(uint32_t n_txn);

@@ -3983,6 +3983,14 @@ static int wire_words(dv_ctx *c, uint32_t nb, Ws *ws, Layout layout) {
     if (!r) layout(c->wire_ws, nb, *ws);
     return r;
 }
+
+// the knobs dv_tpcc_expand accepts (its check of them, on no query)
+static bool wire_tpcc_knobs_ok(const dv_tpcc_params *tp) {
+    uint64_t k, a;
+    uint8_t ty, tb;
+    uint32_t beg;
+    return tp && dv_tpcc_expand(tp, nullptr, 0, 0, &k, &ty, &tb, &a, &beg, nullptr, nullptr) == DV_OK;
+}
 }  // extern "C++"
 
 int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
@@ -3990,7 +3998,7 @@ int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf,
                           const dv_wire_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res) {
     KProfScope kps_(c);
     if (!c || !cfg || !buf || !off || !out || !res) return DV_ERR_ARG;
-    // TPC-C has its own entry (dv_wire_ingest_device_tpcc); CALVIN (batch-id sequencing) stays on the host decoder
+    // TPC-C has its own entry (dv_wire_ingest_device_tpcc), CALVIN its two (dv_wire_ingest_device_calvin*)
     if (cfg->workload != DV_YCSB || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt) return DV_ERR_ARG;
     if (!out->txn_begin || !out->n_acc_dev || !out->max_txn || out->max_txn > kMaxTxn) return DV_ERR_ARG;
     const bool old_form = out->keys && out->types && out->acc_txn;
@@ -4022,15 +4030,9 @@ int dv_wire_ingest_device_tpcc(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t 
                                const dv_wire_tpcc_dev_out *out, uint64_t next_txn, dv_wire_dev_result *res) {
     KProfScope kps_(c);
     if (!c || !cfg || !buf || !off || !out || !res) return DV_ERR_ARG;
-    // CALVIN (batch-id sequencing) stays on the host decoder
-    if (cfg->workload != DV_TPCC || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt || !cfg->tpcc) return DV_ERR_ARG;
-    {  // the knobs dv_tpcc_expand accepts (its check of them, on no query)
-        uint64_t k, a;
-        uint8_t ty, tb;
-        uint32_t beg;
-        if (dv_tpcc_expand(cfg->tpcc, nullptr, 0, 0, &k, &ty, &tb, &a, &beg, nullptr, nullptr) != DV_OK)
-            return DV_ERR_ARG;
-    }
+    // CALVIN sequencer streams have an entry of their own (dv_wire_ingest_device_calvin_tpcc)
+    if (cfg->workload != DV_TPCC || cfg->calvin || !cfg->part_cnt || !cfg->node_cnt || !wire_tpcc_knobs_ok(cfg->tpcc))
+        return DV_ERR_ARG;
     if (!out->txn_begin || !out->n_acc_dev || !out->keys || !out->types || !out->acc_txn || !out->tables || !out->args)
         return DV_ERR_ARG;
     if (!out->max_txn || out->max_txn > kWireTpccMaxTxn) return DV_ERR_ARG;
@@ -4059,7 +4061,7 @@ int dv_wire_ingest_device_calvin(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_
                                  dv_wire_calvin_pos *pos) {
     KProfScope kps_(c);
     if (!c || !cfg || !buf || !off || !out || !pos) return DV_ERR_ARG;
-    // (TPC-C under CALVIN stays on the host decoder)
+    // (TPC-C under CALVIN: dv_wire_ingest_device_calvin_tpcc)
     if (cfg->workload != DV_YCSB || !cfg->calvin || !cfg->part_cnt || !cfg->node_cnt) return DV_ERR_ARG;
     if (!out->txn_begin || !out->keys || !out->types || !out->acc_txn) return DV_ERR_ARG;
     if (out->recs32 && cfg->synth_table_size > (1ull << 31)) return DV_ERR_ARG;
@@ -4080,6 +4082,37 @@ int dv_wire_ingest_device_calvin(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_
     launch_wire_plan_calvin(c->stream, *cfg, buf, buf_len, off, nb, n_batches, *out, *pos, ws);
     r = wire_record_then_emit(c, ws.cres, sizeof(WireCalvinRes), [&] {
         launch_wire_emit_calvin(c->stream, *cfg, buf, off, nb, *out, *pos, ws);
+    });
+    if (r) return r;
+    const WireCalvinRes *h = reinterpret_cast<const WireCalvinRes *>(c->wire_h);
+    *pos = h->pos;
+    return h->status;
+}
+
+int dv_wire_ingest_device_calvin_tpcc(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                                      const uint64_t *off, uint32_t n_batches, const dv_wire_tpcc_dev_out *out,
+                                      dv_wire_calvin_pos *pos) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !buf || !off || !out || !pos) return DV_ERR_ARG;
+    if (cfg->workload != DV_TPCC || !cfg->calvin || !cfg->part_cnt || !cfg->node_cnt || !wire_tpcc_knobs_ok(cfg->tpcc))
+        return DV_ERR_ARG;
+    if (!out->txn_begin || !out->keys || !out->types || !out->acc_txn || !out->tables || !out->args) return DV_ERR_ARG;
+    if (!out->max_txn || out->max_txn > kWireTpccMaxTxn || out->max_acc >= (1ull << 32)) return DV_ERR_ARG;
+    if (pos->batch > n_batches || (pos->batch == n_batches && pos->msg != 0)) return DV_ERR_ARG;
+    if (pos->n_txn > out->max_txn || pos->n_acc > out->max_acc) return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // The YCSB stream's window; at most kWireTpccMaxTxn + 1 mbufs of fewer than
+    // kWireTpccBatchAcc accesses each keep every running sum in 32 bits.
+    const uint32_t window = std::max(out->max_txn - pos->n_txn + 1, 256u);
+    const uint32_t nb = std::min(n_batches - pos->batch, window);
+    WireCalvinWs ws;
+    int r = wire_words(c, nb, &ws, wire_calvin_ws_layout);
+    if (r) return r;
+    const dv_tpcc_params tp = *cfg->tpcc;
+    launch_wire_plan_calvin_tpcc(c->stream, *cfg, tp, buf, buf_len, off, nb, n_batches, *out, *pos, ws);
+    r = wire_record_then_emit(c, ws.cres, sizeof(WireCalvinRes), [&] {
+        launch_wire_emit_calvin_tpcc(c->stream, *cfg, tp, buf, off, nb, *out, *pos, ws);
     });
     if (r) return r;
     const WireCalvinRes *h = reinterpret_cast<const WireCalvinRes *>(c->wire_h);

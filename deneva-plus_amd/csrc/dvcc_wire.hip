@@ -6,7 +6,7 @@
 // dv_wire_ingest_device*).  A batch is at most 4,096 bytes and a short chain of
 // variable-length messages, so a wave takes one: its bytes staged in LDS,
 // the chain walked once (at most 48 links), then every partition and request
-// checked or scattered by all lanes.  Three dialects, four launches each:
+// checked or scattered by all lanes.  Four entries, four launches each:
 //   k_wire_check*  per batch {txns, accesses, longest txn}, the message
 //                  offsets, and the first malformed batch
 //   k_wire_scan*   per chunk of kWireChunk batches: prefixes inside the chunk
@@ -18,10 +18,13 @@
 // k_wire_check_tpcc and k_wire_emit_tpcc, which expand every message to its
 // access list as dv_tpcc_expand does.  CALVIN sequencer streams
 // (dv_wire_ingest_device_calvin, YCSB; k_wire_*_calvin) have a header that
-// carries batch_id, RDONE ends a batch, and the epoch is cut at a message.
-// What the dialects share is written once, in the helpers of the first
-// namespace below: the staging prologues, the chain walk, the partition and
-// request loops, the txn fields, the plan's capacity cut.  A dialect is a
+// carries batch_id, RDONE ends a batch, and the epoch is cut at a message;
+// TPC-C under CALVIN (dv_wire_ingest_device_calvin_tpcc) is the two composed,
+// k_wire_check_calvin_tpcc and k_wire_emit_calvin_tpcc around the stream's
+// scan and plan.  What the dialects share is written once, in the helpers of
+// the unnamed namespaces below: the staging prologues, the chain walk, the
+// partition and request loops, the txn fields, the plan's capacity cut, the
+// TPC-C field checks and expansion, the run of an mbuf.  A dialect is a
 // compile-time parameter (Client, Calvin), never a switch inside a kernel; a
 // helper with a barrier is reached by every wave of its block, live or not.
 // And, for the replies, the committed txns' fields compacted in txn order
@@ -559,6 +562,163 @@ __device__ __forceinline__ uint64_t cust_np_key(uint64_t lo, uint64_t hi, uint64
     return (key << 10) + dist;
 }
 
+// walk_chain's body of a TPC-C query at bo: its item count (at most 62, the
+// 64-bit count it is) and its end behind the items and the tail; 0: refused
+__device__ __forceinline__ uint32_t tpcc_body_end(const Stage &st, uint32_t len, uint32_t bo, uint32_t &n) {
+    if (bo + kTpccBody > len) return 0;
+    const uint64_t n64 = st.u64(bo + kTpccN);
+    if (n64 > DV_TPCC_MAX_OL) return 0;
+    n = (uint32_t)n64;
+    const uint32_t end = bo + kTpccBody + n * kItemBytes + kTpccTail;
+    return end > len ? 0 : end;
+}
+
+// dv_tpcc_expand's checks of a query's fixed fields (body at bo, n items):
+// true where it refuses them.  acc: the accesses it expands to, it: the items
+// still to check -- a NewOrder's (a Payment's are skipped unchecked).
+__device__ __forceinline__ bool tpcc_fields_wrong(const Stage &st, const dv_tpcc_params &tp, uint32_t bo, uint32_t n,
+                                                  uint32_t &acc, uint32_t &it) {
+    const uint64_t tt = st.u64(bo), wh = st.u64(bo + 8), d = st.u64(bo + 16), c = st.u64(bo + 24);
+    bool wrong = !in_1_to(wh, tp.num_wh) || !in_1_to(d, tp.dist_per_wh);
+    if (tt == 1) {
+        wrong |= !in_1_to(st.u64(bo + 40), tp.num_wh) || !in_1_to(st.u64(bo + 48), tp.dist_per_wh) ||
+                 st.u64(bo + kTpccAmount) > kOperandMax;
+        if ((st.u32(bo + kTpccByName) & 0xFFu) != 0)
+            wrong |= !has_nul(st.u64(bo + kTpccLast)) && !has_nul(st.u64(bo + kTpccLast + 8));
+        else
+            wrong |= !in_1_to(c, tp.cust_per_dist);
+        acc = 3;
+    } else if (tt == 2) {
+        // the txn manager walks items[0 .. ol_cnt): the list must hold them, one at least
+        const uint64_t ol_cnt = st.u64(bo + kTpccBody + n * kItemBytes + 2);
+        wrong |= ol_cnt != n || n == 0 || !in_1_to(c, tp.cust_per_dist);
+        acc = 3 + 2 * n;
+        it = n;
+    } else {
+        wrong = true;
+    }
+    return wrong;
+}
+
+// the batch's NewOrder items, one flat range (it[m]: items before message m,
+// io[m]: its first item's offset): an item outside the tables, an operand
+// above 56 bits
+__device__ __forceinline__ bool tpcc_items_wrong(const Stage &st, const dv_tpcc_params &tp, const uint32_t *it,
+                                                 const uint16_t *io, uint32_t tot_it, uint32_t lane) {
+    bool wrong = false;
+    for (uint32_t q = lane; q < tot_it; q += 64) {
+        const uint32_t m = last_le64(it, q);
+        const uint32_t o = io[m] + (q - it[m]) * kItemBytes;
+        wrong |= !in_1_to(st.u64(o), tp.max_items) || !in_1_to(st.u64(o + 8), tp.num_wh) ||
+                 st.u64(o + 16) > kOperandMax;
+    }
+    return wrong;
+}
+
+// what a checked query's lane keeps for the expansion: the keys of its three
+// leading accesses, h_amount, mt = Payment | by name << 1 | w_id's partition
+// << 8 | c_w_id's << 16, its txn type, access count and first item's offset
+struct TpccLead {
+    uint64_t k0, k1, k2, h;
+    uint32_t tt, mt, acc, io;
+};
+__device__ __forceinline__ TpccLead tpcc_lead(const Stage &st, const dv_tpcc_params &tp, uint32_t bo) {
+    TpccLead l{};
+    l.io = bo + kTpccBody;
+    l.tt = st.u32(bo);
+    // (validated: every id below its 32-bit bound)
+    const uint32_t w = st.u32(bo + 8), d = st.u32(bo + 16), c = st.u32(bo + 24);
+    const uint64_t dist = (uint64_t)w * tp.dist_per_wh + d;
+    const uint32_t pw = (w - 1) % tp.part_cnt;  // wh_to_part
+    l.k0 = w;
+    if (l.tt == 1) {
+        const uint32_t c_w = st.u32(bo + 40), c_d = st.u32(bo + 48);
+        const uint64_t c_dist = (uint64_t)c_w * tp.dist_per_wh + c_d;
+        const bool by_name = (st.u32(bo + kTpccByName) & 0xFFu) != 0;
+        l.h = st.u64(bo + kTpccAmount);
+        l.k1 = dist;
+        l.k2 = by_name ? cust_np_key(st.u64(bo + kTpccLast), st.u64(bo + kTpccLast + 8), c_dist)
+                       : c_dist * tp.cust_per_dist + c;
+        l.mt = 1u | (by_name ? 2u : 0u) | ((pw & 0xFFu) << 8) | ((((c_w - 1) % tp.part_cnt) & 0xFFu) << 16);
+        l.acc = 3;
+    } else {
+        l.k1 = dist * tp.cust_per_dist + c;
+        l.k2 = dist;
+        l.mt = (pw & 0xFFu) << 8;
+        l.acc = 3 + 2 * st.u32(bo + kTpccN);
+    }
+    return l;
+}
+
+// a wave's table of its messages' leads (LDS), ac[m]: accesses before message m
+struct TpccLds {
+    uint64_t (*hk)[3], *h;
+    uint32_t *ac, *mt;
+    uint16_t *io;
+    __device__ __forceinline__ void keep(uint32_t lane, const TpccLead &l, uint32_t ac_before) const {
+        ac[lane] = ac_before;
+        io[lane] = (uint16_t)l.io;
+        mt[lane] = l.mt;
+        h[lane] = l.h;
+        hk[lane][0] = l.k0;
+        hk[lane][1] = l.k1;
+        hk[lane][2] = l.k2;
+    }
+};
+
+// the batch's tot_ac accesses in order from access a0 on -- consecutive lanes,
+// consecutive accesses, access j of message m from m's lead and items alone
+// (dv_tpcc_expand's lists); an access of message m belongs to txn t0 + txn_of(m)
+template <class TxnOf>
+__device__ __forceinline__ void emit_tpcc_accesses(const Stage &st, const dv_tpcc_params &tp, const TpccLds &t,
+                                                   uint32_t tot_ac, uint32_t t0, uint32_t a0,
+                                                   const dv_wire_tpcc_dev_out &out, uint32_t lane, TxnOf txn_of) {
+    for (uint32_t r = lane; r < tot_ac; r += 64) {
+        const uint32_t m = last_le64(t.ac, r);
+        const uint32_t j = r - t.ac[m], mt = t.mt[m];
+        uint64_t key, arg;
+        uint32_t type, table, own = (mt >> 8) & 0xFFu;
+        if (j < 3) {
+            key = t.hk[m][j];
+            if (mt & 1u) {  // run_payment_0..5: WAREHOUSE, DISTRICT, CUSTOMER (by id or through the name index)
+                const uint32_t op = j == 0 ? (tp.wh_update ? DV_TOP_PAY_WH : DV_TOP_NONE)
+                                           : (j == 1 ? DV_TOP_PAY_DIST : DV_TOP_PAY_CUST);
+                type = j == 0 && !tp.wh_update ? DV_RD : DV_WR;
+                table = j == 0 ? DV_TPCC_WAREHOUSE
+                               : (j == 1 ? DV_TPCC_DISTRICT : ((mt & 2u) ? DV_TPCC_CUST_LAST : DV_TPCC_CUSTOMER));
+                arg = (uint64_t)op << 56 | t.h[m];
+                if (j == 2) own = (mt >> 16) & 0xFFu;
+            } else {  // new_order_0..5: WAREHOUSE RD, CUSTOMER RD, DISTRICT WR
+                type = j == 2 ? DV_WR : DV_RD;
+                table = j == 0 ? DV_TPCC_WAREHOUSE : (j == 1 ? DV_TPCC_CUSTOMER : DV_TPCC_DISTRICT);
+                arg = j == 2 ? (uint64_t)DV_TOP_NO_DIST << 56 : 0;
+            }
+        } else {  // new_order_6..9: ITEM RD, STOCK WR of item (j - 3) / 2, both with the supply warehouse
+            const uint32_t io = t.io[m] + ((j - 3) >> 1) * kItemBytes;
+            const uint32_t i_id = st.u32(io), sw = st.u32(io + 8);
+            own = ((sw - 1) % tp.part_cnt) & 0xFFu;
+            if (j & 1u) {
+                key = i_id;
+                type = DV_RD;
+                table = DV_TPCC_ITEM;
+                arg = 0;
+            } else {
+                key = (uint64_t)sw * tp.max_items + i_id;
+                type = DV_WR;
+                table = DV_TPCC_STOCK;
+                arg = (uint64_t)DV_TOP_NO_STOCK << 56 | st.u64(io + 16);
+            }
+        }
+        const uint32_t a = a0 + r;
+        out.keys[a] = key;
+        out.types[a] = (uint8_t)type;
+        out.acc_txn[a] = t0 + txn_of(m);
+        out.tables[a] = (uint8_t)table;
+        out.args[a] = arg;
+        if (out.owner) out.owner[a] = (uint8_t)own;
+    }
+}
+
 }  // namespace
 
 // dv_wire_open for a TPC-C cfg: read_client_part, read_tpcc, then
@@ -582,38 +742,12 @@ __global__ __launch_bounds__(kBlock) void k_wire_check_tpcc(dv_wire_cfg cfg, dv_
     if (parse)
         bad = !open_header<Client>(st, cfg, count) ||
               !walk_chain<Client>(st, w.len, count, lane, my, [&](uint32_t bo, uint32_t &n) -> uint32_t {
-                  if (bo + kTpccBody > w.len) return 0;
-                  const uint64_t n64 = st.u64(bo + kTpccN);
-                  if (n64 > DV_TPCC_MAX_OL) return 0;
-                  n = (uint32_t)n64;
-                  const uint32_t end = bo + kTpccBody + n * kItemBytes + kTpccTail;
-                  return end > w.len ? 0 : end;
+                  return tpcc_body_end(st, w.len, bo, n);
               });
     // message m's fixed fields (a Payment's items are skipped unchecked)
     bool wrong = false;
     uint32_t my_acc = 0, my_it = 0;
-    if (parse && !bad && lane < count) {
-        const uint32_t bo = my.bo;
-        const uint64_t tt = st.u64(bo), wh = st.u64(bo + 8), d = st.u64(bo + 16), c = st.u64(bo + 24);
-        wrong = !in_1_to(wh, tp.num_wh) || !in_1_to(d, tp.dist_per_wh);
-        if (tt == 1) {
-            wrong |= !in_1_to(st.u64(bo + 40), tp.num_wh) || !in_1_to(st.u64(bo + 48), tp.dist_per_wh) ||
-                     st.u64(bo + kTpccAmount) > kOperandMax;
-            if ((st.u32(bo + kTpccByName) & 0xFFu) != 0)
-                wrong |= !has_nul(st.u64(bo + kTpccLast)) && !has_nul(st.u64(bo + kTpccLast + 8));
-            else
-                wrong |= !in_1_to(c, tp.cust_per_dist);
-            my_acc = 3;
-        } else if (tt == 2) {
-            // the txn manager walks items[0 .. ol_cnt): the list must hold them, one at least
-            const uint64_t ol_cnt = st.u64(bo + kTpccBody + my.n * kItemBytes + 2);
-            wrong |= ol_cnt != my.n || my.n == 0 || !in_1_to(c, tp.cust_per_dist);
-            my_acc = 3 + 2 * my.n;
-            my_it = my.n;
-        } else {
-            wrong = true;
-        }
-    }
+    if (parse && !bad && lane < count) wrong = tpcc_fields_wrong(st, tp, my.bo, my.n, my_acc, my_it);
     // (a bad batch's lanes hold zeros or a part of the chain: its tables are not read)
     const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my.np, lane);
     const uint32_t ac_in = wave_incl_sum(my_acc, lane);
@@ -626,12 +760,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_check_tpcc(dv_wire_cfg cfg, dv_
     __syncthreads();
     if (parse && !bad) {
         wrong |= parts_wrong<Client>(st, s_pp[wave], s_mo[wave], tot_pp, cfg.part_cnt, lane);
-        for (uint32_t q = lane; q < tot_it; q += 64) {  // items inside the tables, operands of 56 bits
-            const uint32_t m = last_le64(s_it[wave], q);
-            const uint32_t io = s_io[wave][m] + (q - s_it[wave][m]) * kItemBytes;
-            wrong |= !in_1_to(st.u64(io), tp.max_items) || !in_1_to(st.u64(io + 8), tp.num_wh) ||
-                     st.u64(io + 16) > kOperandMax;
-        }
+        wrong |= tpcc_items_wrong(st, tp, s_it[wave], s_io[wave], tot_it, lane);
     }
     bad = bad || __any(wrong);
     if (!w.live) return;
@@ -656,8 +785,9 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_t
     const WaveBatch wb = stage_taken_batch(s_img, buf, off, first, taken);
     const Stage &st = wb.st;
     const uint32_t lane = wb.lane, wave = wb.wave;
-    uint32_t count = 0, src = 0, my_acc = 0, my_io = 0, my_tt = 0, my_mt = 0, t0 = 0, a0 = 0;
-    uint64_t cst = 0, k0 = 0, k1 = 0, k2 = 0, h = 0;
+    uint32_t count = 0, src = 0, t0 = 0, a0 = 0;
+    uint64_t cst = 0;
+    TpccLead my{};
     if (wb.live) {
         src = st.u32(4);
         count = st.u32(8);
@@ -665,92 +795,21 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_tpcc(dv_wire_cfg cfg, dv_t
         if (lane < count) {
             const uint32_t mo = ws.moff[(uint64_t)wb.b * Client::kStride + lane];
             cst = st.u64(mo + Client::kHdr);
-            const uint32_t bo = mo + Client::kFixed + st.u32(mo + Client::kHdr + 8) * 8u;
-            my_io = bo + kTpccBody;
-            my_tt = st.u32(bo);
-            // (validated: every id below its 32-bit bound)
-            const uint32_t w = st.u32(bo + 8), d = st.u32(bo + 16), c = st.u32(bo + 24);
-            const uint64_t dist = (uint64_t)w * tp.dist_per_wh + d;
-            const uint32_t pw = (w - 1) % tp.part_cnt;  // wh_to_part
-            k0 = w;
-            if (my_tt == 1) {
-                const uint32_t c_w = st.u32(bo + 40), c_d = st.u32(bo + 48);
-                const uint64_t c_dist = (uint64_t)c_w * tp.dist_per_wh + c_d;
-                const bool by_name = (st.u32(bo + kTpccByName) & 0xFFu) != 0;
-                h = st.u64(bo + kTpccAmount);
-                k1 = dist;
-                k2 = by_name ? cust_np_key(st.u64(bo + kTpccLast), st.u64(bo + kTpccLast + 8), c_dist)
-                             : c_dist * tp.cust_per_dist + c;
-                my_mt = 1u | (by_name ? 2u : 0u) | ((pw & 0xFFu) << 8) | ((((c_w - 1) % tp.part_cnt) & 0xFFu) << 16);
-                my_acc = 3;
-            } else {
-                k1 = dist * tp.cust_per_dist + c;
-                k2 = dist;
-                my_mt = (pw & 0xFFu) << 8;
-                my_acc = 3 + 2 * st.u32(bo + kTpccN);
-            }
+            my = tpcc_lead(st, tp, mo + Client::kFixed + st.u32(mo + Client::kHdr + 8) * 8u);
         }
     }
-    const uint32_t ac_in = wave_incl_sum(my_acc, lane);
+    const uint32_t ac_in = wave_incl_sum(my.acc, lane);
     const uint32_t tot_ac = __shfl(ac_in, 63, 64);
-    s_ac[wave][lane] = ac_in - my_acc;
-    s_io[wave][lane] = (uint16_t)my_io;
-    s_mt[wave][lane] = my_mt;
-    s_h[wave][lane] = h;
-    s_hk[wave][lane][0] = k0;
-    s_hk[wave][lane][1] = k1;
-    s_hk[wave][lane][2] = k2;
+    const TpccLds t{s_hk[wave], s_h[wave], s_ac[wave], s_mt[wave], s_io[wave]};
+    t.keep(lane, my, ac_in - my.acc);
     __syncthreads();
     if (!wb.live) return;
     if (lane < count) {
-        const uint32_t t = t0 + lane;
-        if (out.txn_type) out.txn_type[t] = (uint8_t)my_tt;
-        emit_txn_fields(out, t, a0 + ac_in - my_acc, worker_txn_id(cfg, next_txn + t), cst, src);
+        const uint32_t txn = t0 + lane;
+        if (out.txn_type) out.txn_type[txn] = (uint8_t)my.tt;
+        emit_txn_fields(out, txn, a0 + ac_in - my.acc, worker_txn_id(cfg, next_txn + txn), cst, src);
     }
-    for (uint32_t r = lane; r < tot_ac; r += 64) {
-        const uint32_t m = last_le64(s_ac[wave], r);
-        const uint32_t j = r - s_ac[wave][m], mt = s_mt[wave][m];
-        uint64_t key, arg;
-        uint32_t type, table, own = (mt >> 8) & 0xFFu;
-        if (j < 3) {
-            key = s_hk[wave][m][j];
-            if (mt & 1u) {  // run_payment_0..5: WAREHOUSE, DISTRICT, CUSTOMER (by id or through the name index)
-                const uint32_t op = j == 0 ? (tp.wh_update ? DV_TOP_PAY_WH : DV_TOP_NONE)
-                                           : (j == 1 ? DV_TOP_PAY_DIST : DV_TOP_PAY_CUST);
-                type = j == 0 && !tp.wh_update ? DV_RD : DV_WR;
-                table = j == 0 ? DV_TPCC_WAREHOUSE
-                               : (j == 1 ? DV_TPCC_DISTRICT : ((mt & 2u) ? DV_TPCC_CUST_LAST : DV_TPCC_CUSTOMER));
-                arg = (uint64_t)op << 56 | s_h[wave][m];
-                if (j == 2) own = (mt >> 16) & 0xFFu;
-            } else {  // new_order_0..5: WAREHOUSE RD, CUSTOMER RD, DISTRICT WR
-                type = j == 2 ? DV_WR : DV_RD;
-                table = j == 0 ? DV_TPCC_WAREHOUSE : (j == 1 ? DV_TPCC_CUSTOMER : DV_TPCC_DISTRICT);
-                arg = j == 2 ? (uint64_t)DV_TOP_NO_DIST << 56 : 0;
-            }
-        } else {  // new_order_6..9: ITEM RD, STOCK WR of item (j - 3) / 2, both with the supply warehouse
-            const uint32_t io = s_io[wave][m] + ((j - 3) >> 1) * kItemBytes;
-            const uint32_t i_id = st.u32(io), sw = st.u32(io + 8);
-            own = ((sw - 1) % tp.part_cnt) & 0xFFu;
-            if (j & 1u) {
-                key = i_id;
-                type = DV_RD;
-                table = DV_TPCC_ITEM;
-                arg = 0;
-            } else {
-                key = (uint64_t)sw * tp.max_items + i_id;
-                type = DV_WR;
-                table = DV_TPCC_STOCK;
-                arg = (uint64_t)DV_TOP_NO_STOCK << 56 | st.u64(io + 16);
-            }
-        }
-        const uint32_t a = a0 + r;
-        out.keys[a] = key;
-        out.types[a] = (uint8_t)type;
-        out.acc_txn[a] = t0 + m;
-        out.tables[a] = (uint8_t)table;
-        out.args[a] = arg;
-        if (out.owner) out.owner[a] = (uint8_t)own;
-    }
+    emit_tpcc_accesses(st, tp, t, tot_ac, t0, a0, out, lane, [](uint32_t m) { return m; });
 }
 
 // cfg as the TPC-C kernels get it: tpcc is a host pointer, the knobs go by value
@@ -794,6 +853,36 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {
     return ((uint64_t)__shfl((uint32_t)(v >> 32), (int)src, 64) << 32) | __shfl((uint32_t)v, (int)src, 64);
 }
 
+// The run of a checked mbuf and what the check keeps of it, for every lane of
+// the wave (lane m: message m in `my`, acc the accesses it becomes as a txn):
+// the lanes from the cursor m0 up to the first whose batch id differs from the
+// cursor's.  The counts are the run's alone, whatever the mbuf holds behind it.
+__device__ __forceinline__ void keep_run(const WireCalvinWs &ws, const WaveBatch &w, bool bad, uint32_t count,
+                                         uint32_t m0, const Msg &my, uint32_t acc) {
+    const uint32_t lane = w.lane, b = w.b;
+    const uint64_t my_bid = !bad && lane < count ? w.st.u64(my.off + kCalBatchId) : 0;
+    // the run: lanes [m0, rend), the first lane behind the cursor whose id is not the cursor's
+    const uint64_t lead = shfl_u64(my_bid, m0 & 63u);
+    const uint64_t differ = __ballot(lane >= m0 && lane < count && my_bid != lead);
+    const uint32_t rend = differ ? (uint32_t)__ffsll((long long)differ) - 1u : count;
+    const bool in_run = lane >= m0 && lane < rend;
+    const bool is_q = in_run && my.rt == DV_WIRE_CL_QRY;
+    const uint32_t txns = (uint32_t)__popcll(__ballot(is_q));
+    const uint32_t rdones = (uint32_t)__popcll(__ballot(in_run && my.rt == DV_WIRE_RDONE));
+    const uint32_t run_n = is_q ? acc : 0u;
+    const uint32_t accs = __shfl(wave_incl_sum(run_n, lane), 63, 64);
+    const uint32_t mx = wave_max(run_n);
+    const uint64_t behind = shfl_u64(my_bid, rend & 63u);
+    if (!w.live) return;
+    keep_batch<Calvin>(ws, w, bad, count, my.off, txns, accs, mx);
+    if (lane == 0) {
+        ws.br[b] = bad ? 0u : rdones;
+        ws.bid[b] = bad ? kNoBatchId : lead;
+        ws.brun[b] = bad ? (uint8_t)0 : (uint8_t)(rend - m0);
+        ws.bflag[b] = bad || rend >= count ? (uint8_t)0 : (uint8_t)(behind > lead ? kRunLater : kRunEarlier);
+    }
+}
+
 }  // namespace
 
 // Whatever dv_wire_open refuses under a CALVIN cfg makes the mbuf bad, whole,
@@ -807,33 +896,12 @@ __global__ __launch_bounds__(kBlock) void k_wire_check_calvin(dv_wire_cfg cfg, c
     __shared__ uint4 s_img[kWireWave][kStageQ];
     __shared__ YcsbTables s_t;
     const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
-    const uint32_t lane = w.lane, b = w.b;
-    const uint32_t m0 = b == 0 ? msg0 : 0;  // the cursor's message (the window's first mbuf is the cursor's)
+    const uint32_t m0 = w.b == 0 ? msg0 : 0;  // the cursor's message (the window's first mbuf is the cursor's)
     uint32_t count = 0, tot_rq;
     Msg my{};
     // every message of the mbuf, in the run or not: it is refused whole
     const bool bad = ycsb_batch_bad<Calvin>(w, cfg, m0, s_t, count, my, tot_rq);
-    const uint64_t my_bid = !bad && lane < count ? w.st.u64(my.off + kCalBatchId) : 0;
-    // the run: lanes [m0, rend), the first lane behind the cursor whose id is not the cursor's
-    const uint64_t lead = shfl_u64(my_bid, m0 & 63u);
-    const uint64_t differ = __ballot(lane >= m0 && lane < count && my_bid != lead);
-    const uint32_t rend = differ ? (uint32_t)__ffsll((long long)differ) - 1u : count;
-    const bool in_run = lane >= m0 && lane < rend;
-    const bool is_q = in_run && my.rt == DV_WIRE_CL_QRY;
-    const uint32_t txns = (uint32_t)__popcll(__ballot(is_q));
-    const uint32_t rdones = (uint32_t)__popcll(__ballot(in_run && my.rt == DV_WIRE_RDONE));
-    const uint32_t run_n = is_q ? my.n : 0u;
-    const uint32_t accs = __shfl(wave_incl_sum(run_n, lane), 63, 64);
-    const uint32_t mx = wave_max(run_n);
-    const uint64_t behind = shfl_u64(my_bid, rend & 63u);
-    if (!w.live) return;
-    keep_batch<Calvin>(ws, w, bad, count, my.off, txns, accs, mx);
-    if (lane == 0) {
-        ws.br[b] = bad ? 0u : rdones;
-        ws.bid[b] = bad ? kNoBatchId : lead;
-        ws.brun[b] = bad ? (uint8_t)0 : (uint8_t)(rend - m0);
-        ws.bflag[b] = bad || rend >= count ? (uint8_t)0 : (uint8_t)(behind > lead ? kRunLater : kRunEarlier);
-    }
+    keep_run(ws, w, bad, count, m0, my, my.n);  // (a query's requests are its accesses)
 }
 
 // chunk blockIdx.x: an mbuf that leads with another id than E has an empty run
@@ -878,9 +946,12 @@ __global__ __launch_bounds__(kBlock) void k_wire_scan_calvin(WireCalvinWs ws, ui
 // its run: the minimum of the first bad mbuf, the first whose run, added to
 // the epoch's and the runs' before it, passes the capacities (the running sums
 // only grow; past the batch's end they count mbufs never reached, and the
-// minimum ignores them) and the first where the batch ends.
+// minimum ignores them) and the first where the batch ends.  Of the call's out
+// it takes what it reads, as k_wire_plan does: the same for both workloads' out.
 __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, uint32_t nb, uint32_t n_batches,
-                                                             uint32_t nc, dv_wire_dev_out out,
+                                                             uint32_t nc, uint32_t max_txn, uint64_t max_acc,
+                                                             uint32_t *__restrict__ txn_begin,
+                                                             uint32_t *__restrict__ n_acc_dev,
                                                              dv_wire_calvin_pos pos) {
     __shared__ uint32_t lds4[4], s_chunk, s_cut, s_max;
     if (threadIdx.x == 0) {
@@ -893,7 +964,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
     const uint32_t tot_r = block_chunk_scan256(ws.cr, nc, lds4);
     __syncthreads();
     // (checked: the rooms are not negative)
-    const uint32_t cut = first_overflow(ws, nb, nc, tot_t, tot_a, out.max_txn - pos.n_txn, out.max_acc - pos.n_acc,
+    const uint32_t cut = first_overflow(ws, nb, nc, tot_t, tot_a, max_txn - pos.n_txn, max_acc - pos.n_acc,
                                         &s_chunk, &s_cut);
     const uint32_t fb = nb ? ws.first[0] : kNoBatch, fe = nb ? ws.first[1] : kNoBatch;
     uint32_t s = fb < cut ? fb : cut;
@@ -938,8 +1009,8 @@ __global__ __launch_bounds__(kBlock) void k_wire_plan_calvin(WireCalvinWs ws, ui
     r.last_end = ends && run > 0 ? m0 + run : kNoBatch;
     r.pad_ = 0;
     *ws.cres = r;
-    out.txn_begin[n_txn] = (uint32_t)n_acc;  // (n_txn <= max_txn, n_acc <= max_acc < 2^32)
-    if (out.n_acc_dev) *out.n_acc_dev = (uint32_t)n_acc;
+    txn_begin[n_txn] = (uint32_t)n_acc;  // (n_txn <= max_txn, n_acc <= max_acc < 2^32)
+    if (n_acc_dev) *n_acc_dev = (uint32_t)n_acc;
 }
 
 // the window's first n_emit mbufs, a wave each: lane m message m from the
@@ -989,17 +1060,28 @@ __global__ __launch_bounds__(kBlock) void k_wire_emit_calvin(dv_wire_cfg cfg, co
                   [tx](uint32_t m) { return (uint32_t)tx[m]; });
 }
 
-void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
-                             const uint64_t *off, uint32_t nb, uint32_t n_batches, const dv_wire_dev_out &out,
-                             const dv_wire_calvin_pos &pos, const WireCalvinWs &ws) {
+// the check, the scan and the plan of a sequencer stream's mbufs, `check` launched with the kernel's own arguments
+template <class Check>
+static void launch_stream_plan(hipStream_t s, uint32_t nb, uint32_t n_batches, uint32_t max_txn, uint64_t max_acc,
+                               uint32_t *txn_begin, uint32_t *n_acc_dev, const dv_wire_calvin_pos &pos,
+                               const WireCalvinWs &ws, Check check) {
     const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk;
     (void)hipMemsetAsync(ws.first, 0xFF, 2 * sizeof(uint32_t), s);  // kNoBatch, both
     if (nb) {
-        DV_LAUNCH(k_wire_check_calvin, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, buf_len, off, pos.batch,
-                  pos.msg, nb, ws);
+        check((nb + kWireWave - 1) / kWireWave);
         DV_LAUNCH(k_wire_scan_calvin, nc, kBlock, 0, s, ws, nb, pos.batch_id);
     }
-    DV_LAUNCH(k_wire_plan_calvin, 1, kBlock, 0, s, ws, nb, n_batches, nc, out, pos);
+    DV_LAUNCH(k_wire_plan_calvin, 1, kBlock, 0, s, ws, nb, n_batches, nc, max_txn, max_acc, txn_begin, n_acc_dev, pos);
+}
+
+void launch_wire_plan_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, uint64_t buf_len,
+                             const uint64_t *off, uint32_t nb, uint32_t n_batches, const dv_wire_dev_out &out,
+                             const dv_wire_calvin_pos &pos, const WireCalvinWs &ws) {
+    launch_stream_plan(s, nb, n_batches, out.max_txn, out.max_acc, out.txn_begin, out.n_acc_dev, pos, ws,
+                       [&](uint32_t grid) {
+                           DV_LAUNCH(k_wire_check_calvin, grid, kBlock, 0, s, cfg, buf, buf_len, off, pos.batch,
+                                     pos.msg, nb, ws);
+                       });
 }
 
 void launch_wire_emit_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_t *buf, const uint64_t *off,
@@ -1008,6 +1090,132 @@ void launch_wire_emit_calvin(hipStream_t s, const dv_wire_cfg &cfg, const uint8_
     if (!nb) return;
     DV_LAUNCH(k_wire_emit_calvin, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, buf, off, pos.batch, pos.msg,
               out, pos.n_txn, (uint32_t)pos.n_acc, ws);
+}
+
+// ---- TPC-C under CALVIN (dv_wire_ingest_device_calvin_tpcc): the two
+// dialects composed.  A CL_QRY is 207 + 8 np + 24 n bytes (Calvin::kFixed, the
+// partitions, kTpccBody, the items, kTpccTail), an RDONE the header alone; the
+// scan and the plan are the YCSB stream's as they are.
+//
+// dv_wire_open for a CALVIN TPC-C cfg, and a cursor below the count.  Lane m
+// checks message m's fixed fields where it is a CL_QRY -- an RDONE lane reads
+// no body byte: what lies behind its header is the next message, or nothing.
+// Two prefix sums live side by side: the NewOrders' items of the whole mbuf,
+// in the run or not (one flat range all lanes check: it is refused whole), and
+// the accesses of the run alone, which keep_run sums.
+__global__ __launch_bounds__(kBlock) void k_wire_check_calvin_tpcc(dv_wire_cfg cfg, dv_tpcc_params tp,
+                                                                   const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                                   const uint64_t *__restrict__ off, uint32_t first,
+                                                                   uint32_t msg0, uint32_t nb, WireCalvinWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint32_t s_it[kWireWave][64], s_pp[kWireWave][64];  // items to check / partitions before message m
+    __shared__ uint16_t s_mo[kWireWave][64], s_io[kWireWave][64];  // message m's offset, its first item's
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane, wave = w.wave;
+    const uint32_t m0 = w.b == 0 ? msg0 : 0;  // the cursor's message (the window's first mbuf is the cursor's)
+    const bool parse = w.live && !w.bad;
+    bool bad = w.bad;
+    uint32_t count = 0;
+    Msg my{};
+    if (parse)
+        bad = !open_header<Calvin>(st, cfg, count) || m0 >= count ||
+              !walk_chain<Calvin>(st, w.len, count, lane, my, [&](uint32_t bo, uint32_t &n) -> uint32_t {
+                  return tpcc_body_end(st, w.len, bo, n);
+              });
+    bool wrong = false;
+    uint32_t my_acc = 0, my_it = 0;
+    if (parse && !bad && lane < count && my.rt == DV_WIRE_CL_QRY)
+        wrong = tpcc_fields_wrong(st, tp, my.bo, my.n, my_acc, my_it);
+    // (an RDONE's lane holds no partitions and no items: np = n = 0 from the walk)
+    const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my.np, lane);
+    const uint32_t tot_it = __shfl(it_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64);
+    s_it[wave][lane] = it_in - my_it;
+    s_pp[wave][lane] = pp_in - my.np;
+    s_mo[wave][lane] = (uint16_t)my.off;
+    s_io[wave][lane] = (uint16_t)(my.bo + kTpccBody);
+    __syncthreads();
+    if (parse && !bad) {
+        wrong |= parts_wrong<Calvin>(st, s_pp[wave], s_mo[wave], tot_pp, cfg.part_cnt, lane);
+        wrong |= tpcc_items_wrong(st, tp, s_it[wave], s_io[wave], tot_it, lane);
+    }
+    bad = bad || __any(wrong);
+    keep_run(ws, w, bad, count, m0, my, my_acc);  // (a txn is at most 3 + 2 * 62 accesses: the per-mbuf byte)
+}
+
+// the window's first n_emit mbufs, a wave each: lane m message m from the
+// cursor (the last mbuf: below the plan's last_end) -- a CL_QRY's txn index a
+// wave prefix over the CL_QRY flags, its boundary, txn type and reply fields,
+// its lead left in LDS; then all lanes the run's accesses (k_wire_emit_tpcc's
+// closed form), behind the epoch's n_txn_in txns and n_acc_in accesses
+__global__ __launch_bounds__(kBlock) void k_wire_emit_calvin_tpcc(dv_wire_cfg cfg, dv_tpcc_params tp,
+                                                                  const uint8_t *__restrict__ buf,
+                                                                  const uint64_t *__restrict__ off, uint32_t first,
+                                                                  uint32_t msg0, dv_wire_tpcc_dev_out out,
+                                                                  uint32_t n_txn_in, uint32_t n_acc_in,
+                                                                  WireCalvinWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint64_t s_hk[kWireWave][64][3], s_h[kWireWave][64];  // message m's leading keys, its h_amount
+    __shared__ uint32_t s_ac[kWireWave][64], s_mt[kWireWave][64];    // accesses before message m, TpccLead::mt
+    __shared__ uint16_t s_io[kWireWave][64], s_tx[kWireWave][64];    // message m's first item, txns before it
+    const uint32_t n_emit = ws.cres->n_emit;
+    if (blockIdx.x * kWireWave >= n_emit) return;
+    const WaveBatch w = stage_taken_batch(s_img, buf, off, first, n_emit);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane, wave = w.wave, b = w.b;
+    uint32_t src = 0, my_q = 0, t0 = 0, a0 = 0;
+    uint64_t tid = 0, cst = 0;
+    TpccLead my{};
+    if (w.live) {
+        src = st.u32(4);
+        const uint32_t count = st.u32(8), last_end = b + 1 == n_emit ? ws.cres->last_end : kNoBatch;
+        const uint32_t m0 = b == 0 ? msg0 : 0, mend = last_end < count ? last_end : count;
+        batch_base(ws, b, t0, a0);
+        t0 += n_txn_in;
+        a0 += n_acc_in;
+        if (lane >= m0 && lane < mend) {
+            const uint32_t mo = ws.moff[(uint64_t)b * Calvin::kStride + lane];
+            if (st.u32(mo) == DV_WIRE_CL_QRY) {
+                my_q = 1;
+                tid = st.u64(mo + kCalTxnId);  // the sequencer's
+                cst = st.u64(mo + Calvin::kHdr);
+                my = tpcc_lead(st, tp, mo + Calvin::kFixed + st.u32(mo + Calvin::kHdr + 8) * 8u);
+            }
+        }
+    }
+    const uint32_t ac_in = wave_incl_sum(my.acc, lane), q_in = wave_incl_sum(my_q, lane);
+    const uint32_t tot_ac = __shfl(ac_in, 63, 64);
+    const TpccLds t{s_hk[wave], s_h[wave], s_ac[wave], s_mt[wave], s_io[wave]};
+    t.keep(lane, my, ac_in - my.acc);
+    s_tx[wave][lane] = (uint16_t)(q_in - my_q);
+    __syncthreads();
+    if (!w.live) return;
+    if (my_q) {
+        const uint32_t txn = t0 + q_in - 1u;
+        if (out.txn_type) out.txn_type[txn] = (uint8_t)my.tt;
+        emit_txn_fields(out, txn, a0 + ac_in - my.acc, tid, cst, src);
+    }
+    const uint16_t *tx = s_tx[wave];
+    emit_tpcc_accesses(st, tp, t, tot_ac, t0, a0, out, lane, [tx](uint32_t m) { return (uint32_t)tx[m]; });
+}
+
+void launch_wire_plan_calvin_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                                  uint64_t buf_len, const uint64_t *off, uint32_t nb, uint32_t n_batches,
+                                  const dv_wire_tpcc_dev_out &out, const dv_wire_calvin_pos &pos,
+                                  const WireCalvinWs &ws) {
+    launch_stream_plan(s, nb, n_batches, out.max_txn, out.max_acc, out.txn_begin, out.n_acc_dev, pos, ws,
+                       [&](uint32_t grid) {
+                           DV_LAUNCH(k_wire_check_calvin_tpcc, grid, kBlock, 0, s, without_tpcc(cfg), tp, buf, buf_len,
+                                     off, pos.batch, pos.msg, nb, ws);
+                       });
+}
+
+void launch_wire_emit_calvin_tpcc(hipStream_t s, const dv_wire_cfg &cfg, const dv_tpcc_params &tp, const uint8_t *buf,
+                                  const uint64_t *off, uint32_t nb, const dv_wire_tpcc_dev_out &out,
+                                  const dv_wire_calvin_pos &pos, const WireCalvinWs &ws) {
+    if (!nb) return;
+    DV_LAUNCH(k_wire_emit_calvin_tpcc, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, without_tpcc(cfg), tp, buf, off,
+              pos.batch, pos.msg, out, pos.n_txn, (uint32_t)pos.n_acc, ws);
 }
 
 // ---- the committed txns' reply fields, compacted in txn order

@@ -299,6 +299,8 @@ SIGNATURES = [
                                                   _P(WireDevResult)]),
     ("dv_wire_ingest_device_calvin", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
                                                     _P(WireDevOut), _P(WireCalvinPos)]),
+    ("dv_wire_ingest_device_calvin_tpcc", ctypes.c_int, [_vp, _P(WireCfg), _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                                         _P(WireTpccDevOut), _P(WireCalvinPos)]),
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),

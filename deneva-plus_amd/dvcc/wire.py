@@ -12,7 +12,10 @@ queue's bytes in, a device-resident epoch out.  TpccDeviceWireIngress does the
 same for TPC-C client batches (dv_wire_ingest_device_tpcc), every message
 expanded to its access list on the device.  CalvinDeviceWireIngress takes
 CALVIN sequencer streams (dv_wire_ingest_device_calvin, YCSB): cut at the
-message where the batch id changes, appended stream by stream in node order.
+message where the batch id changes, appended stream by stream in node order;
+CalvinTpccDeviceWireIngress the same streams of TPC-C queries
+(dv_wire_ingest_device_calvin_tpcc).  No combination of workload and CALVIN is
+left on the host decoder.
 """
 import ctypes
 from dataclasses import dataclass
@@ -377,21 +380,17 @@ class DeviceWireIngress(_DeviceReplies):
         return self._with_replies(ep, n), res.n_taken, res.status
 
 
-class CalvinDeviceWireIngress(_DeviceIngress):
-    """dv_wire_ingest_device_calvin over device buffers of max_txn txns and
-    max_acc accesses on `engine`'s context (YCSB under CALVIN): sequencer
-    streams, cut at message granularity, appended into one open epoch.  An
-    epoch is one sequencer batch per sequencer in origin-major order:
-    feed_buffer once per stream, in node order (or sequence(), which does
-    that), then take().  The epoch's tensors are the ingress's own: the feeds
-    after the next take() overwrite them."""
+class _CalvinStreams(_DeviceIngress):
+    """Sequencer streams, cut at message granularity, appended into one open
+    epoch, whatever the workload (CalvinDeviceWireIngress,
+    CalvinTpccDeviceWireIngress): the cursor and the epoch's totals between
+    calls, sequence() and the CALVIN_ACK replies.  A subclass names its entry
+    point (_entry), builds the call's out (_out) and the epoch (_epoch)."""
 
-    def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
-                 device="cuda"):
-        import torch
-        super().__init__(engine, L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None),
-                         max_txn, max_acc, device)
-        self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
+    _entry = None
+
+    def __init__(self, engine, cfg, max_txn, max_acc, device):
+        super().__init__(engine, cfg, max_txn, max_acc, device)
         self._held = []
         self.status = L.DV_OK
         self._open()
@@ -420,15 +419,13 @@ class CalvinDeviceWireIngress(_DeviceIngress):
             p.batch, p.msg = (pos.batch, pos.msg) if isinstance(pos, L.WireCalvinPos) else pos
         p.n_txn, p.rdone, p.n_acc, p.max_txn_acc = self.n_txn, self.rdone, self.n_acc, self.max_txn_acc
         p.batch_id = L.WIRE_NO_BATCH_ID if self.batch_id is None else self.batch_id
-        q = lambda t: t.data_ptr()  # noqa: E731
-        out = L.WireDevOut(self.max_txn, 0, self.max_acc, q(self.txn_begin), None, None, q(self.keys), q(self.types),
-                           q(self.acc_txn), None, q(self.txn_id), q(self.client_startts), q(self.return_node))
+        out = self._out()
+        entry = getattr(L.lib(), self._entry)
         while True:
             p.stop = 0xFFFFFFFF
-            rc = L.lib().dv_wire_ingest_device_calvin(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(),
-                                                      buf.numel(), off.data_ptr(), off.numel() - 1,
-                                                      ctypes.byref(out), ctypes.byref(p))
-            self._check(rc, p.stop != 0xFFFFFFFF, "dv_wire_ingest_device_calvin")
+            rc = entry(self.engine._ctx, ctypes.byref(self.cfg), buf.data_ptr(), buf.numel(), off.data_ptr(),
+                       off.numel() - 1, ctypes.byref(out), ctypes.byref(p))
+            self._check(rc, p.stop != 0xFFFFFFFF, self._entry)
             if p.stop != L.WIRE_STOP_WINDOW:
                 break
         self._held.append((buf, off))  # (the decode may still read them when this returns)
@@ -443,8 +440,7 @@ class CalvinDeviceWireIngress(_DeviceIngress):
         there), with batch_id, rdone (one per sequencer when the batch is
         complete), txn_begin and the device reply arrays."""
         n, a = self.n_txn, self.n_acc
-        ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n,
-                                      max_txn_acc=self.max_txn_acc)
+        ep = self._epoch(n, a)
         ep.batch_id, ep.rdone = self.batch_id, self.rdone
         ep.txn_begin = self.txn_begin[:n + 1]
         self._with_replies(ep, n)
@@ -463,7 +459,7 @@ class CalvinDeviceWireIngress(_DeviceIngress):
         for (buf, off), cur in zip(streams, cursors):
             p = self.feed_buffer(buf, off, cur)
             if p.stop not in (L.WIRE_STOP_BATCH, L.WIRE_STOP_END):
-                raise L.DvccError(self.status, f"dv_wire_ingest_device_calvin: stop {p.stop} at mbuf {p.batch}, "
+                raise L.DvccError(self.status, f"{self._entry}: stop {p.stop} at mbuf {p.batch}, "
                                                f"message {p.msg}")
             nxt.append((p.batch, p.msg))
         return self.take(), nxt
@@ -478,6 +474,67 @@ class CalvinDeviceWireIngress(_DeviceIngress):
         self.engine._after_torch()
         return _pack_replies(self.cfg, n, ep.batch_id, ep.txn_id.cpu().numpy().view(np.uint64), None,
                              ep.return_node.cpu().numpy().view(np.uint32), None)
+
+
+class CalvinDeviceWireIngress(_CalvinStreams):
+    """dv_wire_ingest_device_calvin over device buffers of max_txn txns and
+    max_acc accesses on `engine`'s context (YCSB under CALVIN): sequencer
+    streams, cut at message granularity, appended into one open epoch.  An
+    epoch is one sequencer batch per sequencer in origin-major order:
+    feed_buffer once per stream, in node order (or sequence(), which does
+    that), then take().  The epoch's tensors are the ingress's own: the feeds
+    after the next take() overwrite them."""
+
+    _entry = "dv_wire_ingest_device_calvin"
+
+    def __init__(self, engine, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, synth_table_size=0, max_req=0,
+                 device="cuda"):
+        import torch
+        super().__init__(engine, L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None),
+                         max_txn, max_acc, device)
+        self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
+
+    def _out(self):
+        q = lambda t: t.data_ptr()  # noqa: E731
+        return L.WireDevOut(self.max_txn, 0, self.max_acc, q(self.txn_begin), None, None, q(self.keys), q(self.types),
+                            q(self.acc_txn), None, q(self.txn_id), q(self.client_startts), q(self.return_node))
+
+    def _epoch(self, n, a):
+        return DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n,
+                                        max_txn_acc=self.max_txn_acc)
+
+
+class CalvinTpccDeviceWireIngress(_CalvinStreams):
+    """dv_wire_ingest_device_calvin_tpcc over device buffers of max_txn txns
+    and max_acc accesses on `engine`'s context (TPC-C under CALVIN): what
+    CalvinDeviceWireIngress does for a sequencer's TPC-C stream, every CL_QRY
+    expanded to its access list following `params` (dv_tpcc_params; the
+    engine's own when it is a TpccEngine running the epoch).  take() returns a
+    DeviceEpoch with tables that also carries args (its operation words),
+    owner and txn_type: run it with run_tpcc_epoch_device(ep, ep.args, ...)."""
+
+    _entry = "dv_wire_ingest_device_calvin_tpcc"
+
+    def __init__(self, engine, params, max_txn, max_acc, node_id=0, node_cnt=1, part_cnt=1, device="cuda"):
+        import torch
+        super().__init__(engine, L.WireCfg(L.TPCC, 1, node_id, node_cnt, part_cnt, 0, 0, ctypes.pointer(params)),
+                         max_txn, max_acc, device)
+        self.params = params
+        self.keys, self.types, self.acc_txn = self._new_accesses(torch.int64, torch.uint8, torch.int32)
+        self.tables, self.args, self.owner = self._new_accesses(torch.uint8, torch.int64, torch.uint8)
+        self.txn_type = self._new(self.max_txn, torch.uint8)
+
+    def _out(self):
+        q = lambda t: t.data_ptr()  # noqa: E731
+        return L.WireTpccDevOut(self.max_txn, 0, self.max_acc, q(self.txn_begin), None, q(self.keys), q(self.types),
+                                q(self.acc_txn), q(self.tables), q(self.args), q(self.txn_type), q(self.owner),
+                                q(self.txn_id), q(self.client_startts), q(self.return_node))
+
+    def _epoch(self, n, a):
+        ep = DeviceEpoch.from_tensors(self.keys[:a], self.types[:a], self.acc_txn[:a], n, tables=self.tables[:a],
+                                      max_txn_acc=self.max_txn_acc)
+        ep.args, ep.owner, ep.txn_type = self.args[:a], self.owner[:a], self.txn_type[:n]
+        return ep
 
 
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):

@@ -61,8 +61,10 @@
  *                               (transport/msg_thread.cpp:53-111)
  *   dv_wire_ingest_device /     the same receive path for YCSB / TPC-C client batches
  *   dv_wire_ingest_device_tpcc /  already in device memory, into a device epoch (and
- *   dv_wire_ingest_device_calvin / CALVIN sequencer streams, cut at their batch ids); the
- *   dv_wire_reply_fields_device committed txns' reply fields compacted for dv_wire_respond
+ *   dv_wire_ingest_device_calvin / CALVIN sequencer streams of either workload, cut at
+ *   dv_wire_ingest_device_calvin_tpcc / their batch ids: no combination is left on the host
+ *   dv_wire_reply_fields_device decoder); the committed txns' reply fields compacted for
+ *                               dv_wire_respond
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
  * the final table state equal a single worker thread running the same epoch
@@ -1131,8 +1133,9 @@ int dv_wire_respond(const dv_wire_cfg *cfg, const dv_wire_epoch *ep, const uint8
  * dv_wire_ingest_device takes YCSB batches and refuses TPC-C, which has an
  * entry of its own below (dv_wire_ingest_device_tpcc); both refuse CALVIN
  * (DV_ERR_ARG), whose sequencer streams -- cut at message granularity -- go
- * through dv_wire_ingest_device_calvin (YCSB; TPC-C under CALVIN stays on the
- * host decoder).
+ * through dv_wire_ingest_device_calvin (YCSB) and
+ * dv_wire_ingest_device_calvin_tpcc (TPC-C): every combination of workload
+ * and CALVIN has a device entry, none is left on the host decoder.
  * The caller's device output buffers and their capacities: */
 typedef struct dv_wire_dev_out {
     uint32_t max_txn, pad_;      /* 1 .. 2^24                                              */
@@ -1310,8 +1313,8 @@ typedef struct dv_wire_calvin_pos {     /* host memory, in/out */
  * for the result record alone, and an epoch over the buffers runs on the same
  * context with no other synchronisation.
  * Refused before any launch (DV_ERR_ARG, *pos untouched): a null pointer,
- * cfg->calvin == 0, a workload other than DV_YCSB (TPC-C under CALVIN stays on
- * the host decoder), zero part_cnt / node_cnt, a missing required array, keys
+ * cfg->calvin == 0, a workload other than DV_YCSB (TPC-C under CALVIN has the
+ * entry below), zero part_cnt / node_cnt, a missing required array, keys
  * / types / acc_txn not all three, recs32 with a table above 2^31, max_txn
  * outside 1 .. 2^24, max_acc >= 2^32, pos->batch > n_batches, msg != 0 at
  * batch == n_batches, pos->n_txn > max_txn, pos->n_acc > max_acc.  A context
@@ -1319,6 +1322,53 @@ typedef struct dv_wire_calvin_pos {     /* host memory, in/out */
 int dv_wire_ingest_device_calvin(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
                                  const uint64_t *off, uint32_t n_batches, const dv_wire_dev_out *out,
                                  dv_wire_calvin_pos *pos);
+
+/* ---- TPC-C under CALVIN on the device: dv_wire_ingest_device_calvin for a
+ * sequencer's TPC-C stream, over dv_wire_tpcc_dev_out's buffers (txn_begin,
+ * keys, types, acc_txn, tables and args required; txn_type, owner, txn_id,
+ * client_startts, return_node and n_acc_dev optional, n_acc_dev receiving the
+ * epoch's total).  The meaning of *pos, of DV_WIRE_STOP_* and of the returned
+ * status is that entry's, word for word: the (mbuf, message) cursor, E, an
+ * mbuf's run, the order of the stoppers mbuf by mbuf (MALFORMED, then CAPACITY
+ * per mbuf -- DV_ERR_ARG while the epoch holds no txn, an empty run never fails
+ * it --, then BATCH / STALE, then WINDOW, then END), the window of
+ * max(max_txn - pos->n_txn + 1, 256) mbufs, the append behind pos->n_txn /
+ * pos->n_acc with nothing written below the append point or at and past the
+ * new totals, txn_begin[n_txn] = n_acc closing the epoch.
+ * For exactly the taken messages keys, types, tables, args, txn_begin,
+ * txn_type, owner, client_startts and return_node equal what
+ * dv_wire_decode_batches writes under a calvin = 1, DV_TPCC cfg, bit for bit;
+ * txn_id is the message's own (the sequencer's: there is no next_txn), acc_txn
+ * and txn_begin carry epoch numbering, and pos->max_txn_acc is the longest
+ * expanded txn.  A CL_QRY expands as in dv_wire_ingest_device_tpcc
+ * (dv_tpcc_expand's lists, cfg->tpcc read on the host and passed by value).
+ * Malformed is the union of the two entries' rules, applied to every message
+ * of the mbuf, in the run or not, in front of the cursor included: whatever
+ * dv_wire_open refuses under this cfg -- header, count, exact fill of the
+ * length; an rtype other than CL_QRY / RDONE; a batch id of UINT64_MAX; np <=
+ * 64 and partitions below part_cnt; n <= 62 (the 64-bit count, before n * 24);
+ * txn_type 1 or 2 (the 64-bit value); every id as v - 1 < bound in 64 bits;
+ * h_amount < 2^56; a NUL in the name of a Payment by name; ol_cnt == n >= 1 for
+ * a NewOrder and each of its items' id, supply warehouse and 56-bit quantity --
+ * plus a bad off and a cursor at or past the mbuf's count.  A Payment's items
+ * and the fields the expansion never reads are not looked at, as on the host.
+ * Sizes, fixed by the format: the header is 84 bytes and the fixed part 100, a
+ * CL_QRY 207 + 8 np + 24 n bytes, an RDONE 84; an mbuf's 4,084 message bytes
+ * hold at most 48 messages and at most 19 txns; a message of n items is 207 +
+ * 24 n bytes at least for 3 + 2 n accesses at most -- 12 bytes an access at
+ * least, at most 340 accesses an mbuf; the longest txn is 3 + 2 * 62 = 127
+ * accesses.  max_txn <= 2^23, as in dv_wire_ingest_device_tpcc: the window is
+ * then at most 2^23 + 1 mbufs and (2^23 + 1) x 341 < 2^32 keeps every running
+ * sum of the mbufs' counts in 32 bits.
+ * Refused before any launch (DV_ERR_ARG, *pos untouched): a null pointer,
+ * cfg->calvin == 0, a workload other than DV_TPCC, a null cfg->tpcc or knobs
+ * dv_tpcc_expand refuses, a missing required array, zero part_cnt / node_cnt,
+ * max_txn outside 1 .. 2^23, max_acc >= 2^32, pos->batch > n_batches, msg != 0
+ * at batch == n_batches, pos->n_txn > max_txn, pos->n_acc > max_acc.  A context
+ * in the middle of an epoch: DV_ERR_STATE. */
+int dv_wire_ingest_device_calvin_tpcc(dv_ctx *ctx, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
+                                      const uint64_t *off, uint32_t n_batches, const dv_wire_tpcc_dev_out *out,
+                                      dv_wire_calvin_pos *pos);
 
 /* The reply fields of the committed txns (commit[t] != 0, device bytes) of an
  * epoch ingested on the device: txn_id / client_startts / return_node
