@@ -90,10 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_carry_scan(uint32_t *__restrict__ bt
 }
 
 // every carried txn with a new id below max_txn is copied; the last one
-// reports the carried epoch's size (tot[0] txns, tot[1] accesses).  A wave
-// holds 64 consecutive txns, whose carried accesses are contiguous in the
-// output: its lanes copy them together (a prefix sum of the lengths picks
-// each access's txn), so reads and writes are coalesced.
+// reports the carried epoch's size (tot[0] txns, tot[1] accesses).
 template <bool ARGS>
 __global__ __launch_bounds__(kBlock) void k_carry_copy(
     const uint8_t *__restrict__ status, const uint32_t *__restrict__ tb_start,
@@ -121,96 +118,59 @@ __global__ __launch_bounds__(kBlock) void k_carry_copy(
     }
     if (!cr || id >= max_txn) len = 0;  // (ids grow with t: the cap cuts a suffix)
     else if (otb) otb[id] = pos;        // (tb form: the carried txn's boundary, dv_epoch_dev::txn_begin)
-#ifndef DVCC_CARRY_COPY_WAVE
     // The block's txns hold one contiguous run of source accesses: the block
     // streams it (coalesced loads and stores), each access going to its txn's
     // destination plus its offset in the txn.  An access's txn: the last one
     // starting at or before it, by a binary search over the block's starts in
     // LDS -- made monotone by a suffix minimum, since an empty txn's range
-    // (never written by the probe) may hold anything.  (The wave form below
+    // (never written by the probe) may hold anything.  (An earlier form
     // spread each wave's carried accesses over its lanes by a shuffle search:
     // at a ~97 % carry rate that search, not the bytes, set its time.)
-    {
-        constexpr uint32_t kNone = 0xFFFFFFFFu;
-        __shared__ uint32_t s_a0[kCarryTpb], s_id[kCarryTpb], s_sh[kCarryTpb], s_w[2][kCarryTpb / 64];
-        const uint32_t tid = threadIdx.x, wave = tid >> 6;
-        const uint32_t a0s = t < n_txn ? tb_start[t] : 0u;
-        const uint32_t src_len = t < n_txn ? tb_end[t] - a0s : 0u;
-        uint32_t v = src_len ? a0s : kNone;  // suffix min of the non-empty txns' starts
-        uint32_t e = src_len ? a0s + src_len : 0u;  // and the block's end of accesses (max)
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_down(v, off, 64), oe = __shfl_down(e, off, 64);
-            if (lane + (uint32_t)off < 64u) {
-                v = o < v ? o : v;
-                e = oe > e ? oe : e;
-            }
-        }
-        if (lane == 0) {
-            s_w[0][wave] = v;  // (lane 0: the wave's whole suffix)
-            s_w[1][wave] = e;
-        }
-        __syncthreads();
-        uint32_t hi = 0;
-        for (uint32_t w = 0; w < kCarryTpb / 64; w++) {
-            if (w > wave) v = s_w[0][w] < v ? s_w[0][w] : v;
-            hi = s_w[1][w] > hi ? s_w[1][w] : hi;
-        }
-        s_a0[tid] = v;
-        s_id[tid] = len ? id : kNone;
-        s_sh[tid] = pos - a0;  // (mod 2^32: destination = source + shift)
-        __syncthreads();
-        const uint32_t lo = s_a0[0];
-        for (uint32_t i = lo + tid; lo != kNone && i < hi; i += kCarryTpb) {
-            uint32_t k = 0;
-#pragma unroll
-            for (uint32_t w = kCarryTpb / 2; w > 0; w >>= 1)
-                if (s_a0[k + w] <= i) k += w;
-            const uint32_t sid = s_id[k];
-            if (sid == kNone) continue;
-            const uint32_t o = i + s_sh[k];
-            if (orecs) orecs[o] = recs[i];  // tb form: the 4-byte records (key | write << 31)
-            if (!okeys) continue;
-            okeys[o] = keys[i];
-            otypes[o] = types[i];
-            otxn[o] = sid;
-            if (tables) otables[o] = tables[i];
-            if (ARGS) oargs[o] = args[i];  // (TPC-C: the operation word, an 8-byte stream like the keys)
-        }
-        return;
-    }
-#endif
-    uint32_t incl = len;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    __shared__ uint32_t s_a0[kCarryTpb], s_id[kCarryTpb], s_sh[kCarryTpb], s_w[2][kCarryTpb / 64];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    const uint32_t a0s = t < n_txn ? tb_start[t] : 0u;
+    const uint32_t src_len = t < n_txn ? tb_end[t] - a0s : 0u;
+    uint32_t v = src_len ? a0s : kNone;  // suffix min of the non-empty txns' starts
+    uint32_t e = src_len ? a0s + src_len : 0u;  // and the block's end of accesses (max)
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += o;
-    }
-    const uint32_t pre = incl - len, wtot = __shfl(incl, 63, 64);
-    // the wave's first carried access goes where its first carried txn's does
-    const uint64_t first = __ballot(len != 0);
-    if (!first) return;
-    const uint32_t wpos = __shfl(pos, (int)__builtin_ctzll(first), 64);
-    for (uint32_t g0 = 0; g0 < wtot; g0 += 64) {  // wave-uniform trips: shuffles read every lane
-        const uint32_t g = g0 + lane;
-        uint32_t src = 0;
-#pragma unroll
-        for (uint32_t w = 32; w > 0; w >>= 1) {
-            const uint32_t cand = src + w;
-            const uint32_t pv = __shfl(pre, (int)(cand & 63u), 64);
-            if (cand < 64 && pv <= g) src = cand;
+        const uint32_t o = __shfl_down(v, off, 64), oe = __shfl_down(e, off, 64);
+        if (lane + (uint32_t)off < 64u) {
+            v = o < v ? o : v;
+            e = oe > e ? oe : e;
         }
-        const uint32_t sa0 = __shfl(a0, (int)src, 64), spre = __shfl(pre, (int)src, 64);
-        const uint32_t sid = __shfl(id, (int)src, 64);
-        if (g >= wtot) continue;
-        const uint32_t in = sa0 + (g - spre), o = wpos + g;
-        if (orecs) orecs[o] = recs[in];  // tb form: the 4-byte records (key | write << 31)
+    }
+    if (lane == 0) {
+        s_w[0][wave] = v;  // (lane 0: the wave's whole suffix)
+        s_w[1][wave] = e;
+    }
+    __syncthreads();
+    uint32_t hi = 0;
+    for (uint32_t w = 0; w < kCarryTpb / 64; w++) {
+        if (w > wave) v = s_w[0][w] < v ? s_w[0][w] : v;
+        hi = s_w[1][w] > hi ? s_w[1][w] : hi;
+    }
+    s_a0[tid] = v;
+    s_id[tid] = len ? id : kNone;
+    s_sh[tid] = pos - a0;  // (mod 2^32: destination = source + shift)
+    __syncthreads();
+    const uint32_t lo = s_a0[0];
+    for (uint32_t i = lo + tid; lo != kNone && i < hi; i += kCarryTpb) {
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t w = kCarryTpb / 2; w > 0; w >>= 1)
+            if (s_a0[k + w] <= i) k += w;
+        const uint32_t sid = s_id[k];
+        if (sid == kNone) continue;
+        const uint32_t o = i + s_sh[k];
+        if (orecs) orecs[o] = recs[i];  // tb form: the 4-byte records (key | write << 31)
         if (!okeys) continue;
-        okeys[o] = keys[in];
-        otypes[o] = types[in];
+        okeys[o] = keys[i];
+        otypes[o] = types[i];
         otxn[o] = sid;
-        if (tables) otables[o] = tables[in];
-        if (ARGS) oargs[o] = args[in];
+        if (tables) otables[o] = tables[i];
+        if (ARGS) oargs[o] = args[i];  // (TPC-C: the operation word, an 8-byte stream like the keys)
     }
 }
 
@@ -230,7 +190,7 @@ __global__ void k_carry_total(const uint8_t *__restrict__ status, uint32_t n_txn
     }
 }
 
-// ---- the closed loop on the device (dv_epoch_refill): the next epoch is the
+// ---- the closed loop on the device (dv_epoch_run_closed_loop): the next epoch is the
 // carried txns (as above, capped at n_out), then fresh txns taken in order
 // from a pool, starting at a device-side cursor that wraps around the pool.
 // Nothing is read back: the epoch's access count stays on the device
@@ -436,42 +396,45 @@ __global__ __launch_bounds__(kBlock) void k_track_fresh(const uint32_t *__restri
     if (prev) track_fold(tr);
 }
 
-void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                   uint32_t n_txn, const uint64_t *keys, const uint8_t *types, const uint8_t *tables,
-                   const uint64_t *pkeys, const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptxn,
-                   const uint32_t *ptb, uint32_t pool_n, uint32_t *cursor, uint32_t n_out, uint64_t fresh_bound,
-                   uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
-                   uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs,
-                   const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const uint64_t *args,
-                   const uint64_t *pargs, uint64_t *oargs, const RefillTrack *trk) {
-    const uint32_t nb = carry_blocks(n_txn);
+static void launch_refill_backoff(hipStream_t s, const RefillReq &q);
+
+void launch_refill(hipStream_t s, const RefillReq &q) {
+    if (q.bo) return launch_refill_backoff(s, q);
+    const DecidedEpoch &e = q.ep;
+    const AccessCols &in = q.in, &p = q.pool.cols;
+    const AccessOut &o = q.out;
+    uint32_t *const bt = q.ws.bt, *const ba = q.ws.ba, *const tot = q.ws.tot;
+    const uint32_t nb = carry_blocks(e.n_txn);
     if (nb) {
-        DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba);
+        DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba);
         DV_LAUNCH(k_carry_scan, 1, kBlock, 0, s, bt, ba, nb);
     }
-    DV_LAUNCH(k_refill_plan, 1, 64, 0, s, status, n_txn, bt, nb, tot, n_out, cursor, pool_n, ctr);
+    DV_LAUNCH(k_refill_plan, 1, 64, 0, s, e.status, e.n_txn, bt, nb, tot, q.n_out, q.pool.cursor, q.pool.n, e.ctr);
     const uint32_t *skip = tot + 4;
     const uint64_t *no_args = nullptr;
-    if (nb && oargs)
-        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, n_out, keys, types,
-                  tables, okeys, otypes, otxn, otables, tot, skip, recs, orecs, otb, args, oargs);
+    if (nb && o.args)
+        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba, q.n_out,
+                  in.keys, in.types, in.tables, o.keys, o.types, o.txn, o.tables, tot, skip, in.recs, o.recs, o.tb,
+                  in.args, o.args);
     else if (nb)
-        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, n_out, keys, types,
-                  tables, okeys, otypes, otxn, otables, tot, skip, recs, orecs, otb, no_args, oargs);
-    const uint64_t g = (fresh_bound + kBlock - 1) / kBlock;
+        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba, q.n_out,
+                  in.keys, in.types, in.tables, o.keys, o.types, o.txn, o.tables, tot, skip, in.recs, o.recs, o.tb,
+                  no_args, o.args);
+    const uint64_t g = (q.acc_bound + kBlock - 1) / kBlock;
     const uint32_t grid = (uint32_t)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-    if (oargs)
-        DV_LAUNCH((k_refill_fresh<true>), grid, kBlock, 0, s, pkeys, ptypes, ptables, ptxn, ptb, pool_n, tot, n_out,
-                  okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb, pargs, oargs);
+    if (o.args)
+        DV_LAUNCH((k_refill_fresh<true>), grid, kBlock, 0, s, p.keys, p.types, p.tables, p.txn, q.pool.tb, q.pool.n,
+                  tot, q.n_out, o.keys, o.types, o.txn, o.tables, o.n_acc_dev, p.recs, o.recs, o.tb, p.args, o.args);
     else
-        DV_LAUNCH((k_refill_fresh<false>), grid, kBlock, 0, s, pkeys, ptypes, ptables, ptxn, ptb, pool_n, tot, n_out,
-                  okeys, otypes, otxn, otables, n_acc_dev, precs, orecs, otb, no_args, oargs);
-    if (!trk) return;
+        DV_LAUNCH((k_refill_fresh<false>), grid, kBlock, 0, s, p.keys, p.types, p.tables, p.txn, q.pool.tb, q.pool.n,
+                  tot, q.n_out, o.keys, o.types, o.txn, o.tables, o.n_acc_dev, p.recs, o.recs, o.tb, no_args, o.args);
+    if (!q.trk) return;
     constexpr uint32_t wpb = kBlock / 64;  // (k_track_carry: a wave per carry block)
-    if (nb) DV_LAUNCH(k_track_carry, (nb + wpb - 1) / wpb, kBlock, 0, s, status, n_txn, bt, tot, n_out, *trk);
-    const uint32_t gf = (n_out + kBlock - 1) / kBlock;
-    DV_LAUNCH(k_track_fresh, gf < 1 ? 1 : (gf > 1024 ? 1024 : gf), kBlock, 0, s, tot, n_out, pool_n, nb ? 1 : 0,
-              *trk);
+    if (nb)
+        DV_LAUNCH(k_track_carry, (nb + wpb - 1) / wpb, kBlock, 0, s, e.status, e.n_txn, bt, tot, q.n_out, *q.trk);
+    const uint32_t gf = (q.n_out + kBlock - 1) / kBlock;
+    DV_LAUNCH(k_track_fresh, gf < 1 ? 1 : (gf > 1024 ? 1024 : gf), kBlock, 0, s, tot, q.n_out, q.pool.n, nb ? 1 : 0,
+              *q.trk);
 }
 
 // ---- back-off (dv_closed_loop_backoff): the reference's AbortQueue::enqueue
@@ -838,26 +801,27 @@ __global__ __launch_bounds__(kBlock) void k_bo_fold(const uint32_t *__restrict__
     if (sum) bo.counters[2] += sum;
 }
 
-void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn, const uint64_t *pkeys,
-                           const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptb, uint32_t pool_n,
-                           uint32_t *cursor, uint32_t n_out, uint64_t acc_cap, uint64_t *okeys, uint8_t *otypes,
-                           uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev, uint32_t *tot, const Counters *ctr,
-                           const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const RefillTrack &trk,
-                           const RefillBackoff &bo) {
+static void launch_refill_backoff(hipStream_t s, const RefillReq &q) {
+    const RefillTrack &trk = *q.trk;
+    const RefillBackoff &bo = *q.bo;
+    const AccessCols &p = q.pool.cols;
+    const AccessOut &o = q.out;
+    const uint32_t n_txn = q.ep.n_txn, n_out = q.n_out, pool_n = q.pool.n;
+    uint32_t *const tot = q.ws.tot;
     const uint32_t nb = carry_blocks(n_txn), nbo = carry_blocks(n_out);
     constexpr uint32_t wpb = kBlock / 64;  // (k_bo_park: a wave per carry block)
     if (nb) {
-        DV_LAUNCH(k_bo_count, nb, kBlock, 0, s, status, bo.aborts, n_txn, nb, bo.lgD, bo.cls);
+        DV_LAUNCH(k_bo_count, nb, kBlock, 0, s, q.ep.status, bo.aborts, n_txn, nb, bo.lgD, bo.cls);
         DV_LAUNCH(k_bo_scan, bo.lgD + 1, kBlock, 0, s, bo.cls, nb, bo.bw + BW_CTOT);
     }
-    DV_LAUNCH(k_bo_plan, 1, 64, 0, s, nb ? 1 : 0, trk.k_next, n_out, cursor, pool_n, ctr, tot, bo);
-    if (nb) DV_LAUNCH(k_bo_park, (nb + wpb - 1) / wpb, kBlock, 0, s, status, n_txn, nb, tot, trk, bo);
+    DV_LAUNCH(k_bo_plan, 1, 64, 0, s, nb ? 1 : 0, trk.k_next, n_out, q.pool.cursor, pool_n, q.ep.ctr, tot, bo);
+    if (nb) DV_LAUNCH(k_bo_park, (nb + wpb - 1) / wpb, kBlock, 0, s, q.ep.status, n_txn, nb, tot, trk, bo);
     const uint32_t gs = (bo.cap + kBlock - 1) / kBlock;
     DV_LAUNCH(k_bo_spill, gs < 1 ? 1 : (gs > 1024 ? 1024 : gs), kBlock, 0, s, tot, bo);
-    DV_LAUNCH(k_bo_gather_count, nbo, kBlock, 0, s, tot, n_out, ptb, pool_n, trk.oids, trk.k_next, bo);
+    DV_LAUNCH(k_bo_gather_count, nbo, kBlock, 0, s, tot, n_out, q.pool.tb, pool_n, trk.oids, trk.k_next, bo);
     DV_LAUNCH(k_bo_scan, 1, kBlock, 0, s, bo.gb, nbo, bo.bw + BW_GTOT);
-    DV_LAUNCH(k_bo_gather_copy, nbo, kBlock, 0, s, tot, n_out, trk.oids, pkeys, ptypes, ptables, ptb, pool_n, precs,
-              okeys, otypes, otxn, otables, orecs, otb, n_acc_dev, acc_cap, bo);
+    DV_LAUNCH(k_bo_gather_copy, nbo, kBlock, 0, s, tot, n_out, trk.oids, p.keys, p.types, p.tables, q.pool.tb, pool_n,
+              p.recs, o.keys, o.types, o.txn, o.tables, o.recs, o.tb, o.n_acc_dev, q.acc_bound, bo);
     if (nb) {
         const uint32_t gf = (trk.n_bins + 4 + kBlock - 1) / kBlock;
         DV_LAUNCH(k_bo_fold, gf, kBlock, 0, s, tot, trk, bo);
@@ -893,27 +857,29 @@ void launch_txn_ranges(hipStream_t s, const uint32_t *acc_txn, uint64_t n, uint3
 
 uint32_t carry_blocks(uint32_t n_txn) { return n_txn ? (n_txn + kCarryTpb - 1) / kCarryTpb : 0; }
 
-void launch_carry(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                  uint32_t n_txn, uint32_t max_txn, const uint64_t *keys, const uint8_t *types,
-                  const uint8_t *tables, uint64_t *okeys, uint8_t *otypes, uint32_t *otxn,
-                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot, const uint64_t *args,
-                  uint64_t *oargs) {
-    const uint32_t nb = carry_blocks(n_txn);
+void launch_carry(hipStream_t s, const CarryReq &q) {
+    const DecidedEpoch &e = q.ep;
+    const AccessCols &in = q.in;
+    const AccessOut &o = q.out;
+    uint32_t *const bt = q.ws.bt, *const ba = q.ws.ba, *const tot = q.ws.tot;
+    const uint32_t nb = carry_blocks(e.n_txn);
     if (!nb) {
         (void)hipMemsetAsync(tot, 0, 3 * sizeof(uint32_t), s);
         return;
     }
-    DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba);
+    DV_LAUNCH(k_carry_count, nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba);
     DV_LAUNCH(k_carry_scan, 1, kBlock, 0, s, bt, ba, nb);
-    DV_LAUNCH(k_carry_total, 1, 64, 0, s, status, n_txn, bt, nb, tot);
+    DV_LAUNCH(k_carry_total, 1, 64, 0, s, e.status, e.n_txn, bt, nb, tot);
     const uint32_t *none = nullptr;
     uint32_t *onone = nullptr;
-    if (oargs)
-        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, max_txn, keys,
-                  types, tables, okeys, otypes, otxn, otables, tot, none, none, onone, onone, args, oargs);
+    if (o.args)
+        DV_LAUNCH((k_carry_copy<true>), nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba, q.max_txn,
+                  in.keys, in.types, in.tables, o.keys, o.types, o.txn, o.tables, tot, none, none, onone, onone,
+                  in.args, o.args);
     else
-        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, status, tb_start, tb_end, n_txn, bt, ba, max_txn, keys,
-                  types, tables, okeys, otypes, otxn, otables, tot, none, none, onone, onone, args, oargs);
+        DV_LAUNCH((k_carry_copy<false>), nb, kBlock, 0, s, e.status, e.tb_start, e.tb_end, e.n_txn, bt, ba, q.max_txn,
+                  in.keys, in.types, in.tables, o.keys, o.types, o.txn, o.tables, tot, none, none, onone, onone,
+                  in.args, o.args);
 }
 
 }  // namespace dvcc

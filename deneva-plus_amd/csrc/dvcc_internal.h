@@ -539,35 +539,73 @@ int comm_combine_errors(dv_ctx *c);  // dvcc_comm.hip
 void comm_free(dvcc::DvComm *m);
 namespace dvcc {
 
-// abort carry-over (dvcc_carry.hip): the accesses of the txns whose status is
-// not committed, in sequence order and renumbered from 0, capped at max_txn
-// txns, into o*; tot (3 words, device) = carried txns, their accesses, and the
-// carried txns before the cap.  bt/ba: carry_blocks(n_txn) words each.
-// oargs (TPC-C): the carried accesses' operation words too, from args.
+// ---- abort carry-over and the closed loop's refill (dvcc_carry.hip).  Their
+// requests are plain aggregates of device pointers; a NULL column is not read
+// or not written.
+// An epoch's access columns as read: args (TPC-C) the accesses' operation
+// words, recs the tb form's 4-byte records (dv_epoch_dev::recs32).
+struct AccessCols {
+    const uint64_t *keys;
+    const uint8_t *types, *tables;
+    const uint32_t *txn, *recs;
+    const uint64_t *args;
+};
+// ... and as written.  keys NULL: only the tb form (keys / types / txn / tables
+// are not written).  tb form (recs, tb): the epoch as 4-byte records and its
+// txn boundaries tb[0..n_out] (dv_epoch_dev::txn_begin).  args (TPC-C, never
+// with the tb form): the operation words too.  *n_acc_dev = the accesses
+// written (the refill only).
+struct AccessOut {
+    uint64_t *keys;
+    uint8_t *types;
+    uint32_t *txn;
+    uint8_t *tables;
+    uint32_t *recs, *tb;
+    uint64_t *args;
+    uint32_t *n_acc_dev;
+};
+// The decided epoch: its txns' statuses and access ranges.  ctr (the refill
+// only): a halted or rejected epoch makes every refill kernel a no-op; NULL
+// with n_txn 0 for the loop's first epoch.
+struct DecidedEpoch {
+    const uint8_t *status;
+    const uint32_t *tb_start, *tb_end;
+    uint32_t n_txn;
+    const Counters *ctr;
+};
+// The pool of fresh txns: n txns, tb their n + 1 access offsets, taken from
+// *cursor on (advanced, wrapping).
+struct RefillPool {
+    AccessCols cols;
+    const uint32_t *tb;
+    uint32_t n;
+    uint32_t *cursor;
+};
+// bt / ba: carry_blocks(n_txn) words each; tot (device): 3 words for the carry
+// -- carried txns, their accesses, and the carried txns before the cap --
+// kRefillTot words for the refill.
+struct CarryWs {
+    uint32_t *bt, *ba, *tot;
+};
+constexpr uint32_t kRefillTot = 6;
 uint32_t carry_blocks(uint32_t n_txn);
-void launch_carry(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                  uint32_t n_txn, uint32_t max_txn, const uint64_t *keys, const uint8_t *types,
-                  const uint8_t *tables, uint64_t *okeys, uint8_t *otypes, uint32_t *otxn,
-                  uint8_t *otables, uint32_t *bt, uint32_t *ba, uint32_t *tot, const uint64_t *args = nullptr,
-                  uint64_t *oargs = nullptr);
+
+// abort carry-over: the accesses of the txns of ep whose status is not
+// committed, in sequence order and renumbered from 0, capped at max_txn txns,
+// from `in` into `out`
+struct CarryReq {
+    DecidedEpoch ep;
+    AccessCols in;
+    uint32_t max_txn;
+    AccessOut out;
+    CarryWs ws;
+};
+void launch_carry(hipStream_t s, const CarryReq &q);
 
 // per-txn access ranges of a batch from its acc_txn (dv_epoch_group_carry)
 void launch_txn_ranges(hipStream_t s, const uint32_t *acc_txn, uint64_t n, uint32_t n_txn, uint32_t *tbs,
                        uint32_t *tbe);
 
-// the closed loop (dv_epoch_refill): the aborted txns of the decided epoch
-// (status, access ranges, its keys / types / tables) carried first, capped
-// at n_out, then n_out - C fresh txns of the pool (pkeys ... ptb, pool_n txns)
-// from *cursor on (advanced, wrapping), into o*; *n_acc_dev = the accesses
-// written.  fresh_bound: a bound on the fresh accesses (grid size).  A halted
-// or rejected epoch (Counters; NULL for the loop's first epoch, n_txn 0) makes
-// every kernel a no-op.  tot: kRefillTot words.  tb form (orecs, otb): the
-// next epoch as 4-byte records (recs: the previous epoch's, precs: the
-// pool's) and its txn boundaries otb[0..n_out]; okeys NULL: only that form
-// (o{keys,types,txn,tables} are not written).  oargs (TPC-C, never with the
-// tb form): the operation words of the carried (args) and fresh (pargs)
-// accesses too.
-constexpr uint32_t kRefillTot = 6;
 // The loop tracker's words for one refill (dv_closed_loop_track): the previous
 // epoch's identity words (ids; NULL with no previous epoch) and the next
 // one's (oids), the commit log, and the epoch numbers -- k: the epoch just
@@ -589,15 +627,6 @@ struct RefillTrack {
     uint32_t k, k_next, L;
     uint32_t *part;
 };
-void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_start, const uint32_t *tb_end,
-                   uint32_t n_txn, const uint64_t *keys, const uint8_t *types, const uint8_t *tables,
-                   const uint64_t *pkeys, const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptxn,
-                   const uint32_t *ptb, uint32_t pool_n, uint32_t *cursor, uint32_t n_out, uint64_t fresh_bound,
-                   uint64_t *okeys, uint8_t *otypes, uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev,
-                   uint32_t *bt, uint32_t *ba, uint32_t *tot, const Counters *ctr, const uint32_t *recs = nullptr,
-                   const uint32_t *precs = nullptr, uint32_t *orecs = nullptr, uint32_t *otb = nullptr,
-                   const uint64_t *args = nullptr, const uint64_t *pargs = nullptr, uint64_t *oargs = nullptr,
-                   const RefillTrack *trk = nullptr);
 
 // The back-off ring's words for one refill (dv_closed_loop_backoff; always
 // with a RefillTrack): behind epoch trk->k (n_txn txns; 0: none, the loop's
@@ -605,7 +634,7 @@ void launch_refill(hipStream_t s, const uint8_t *status, const uint32_t *tb_star
 // min(2^(a-1), D) epochs ahead, and epoch trk->k_next is the ring slot that
 // falls due, capped at n_out, then fresh pool txns; every txn's accesses are
 // read from the pool by its identity word's src.  A different launch chain
-// from launch_refill's (nothing is copied from the decided epoch), no-ops
+// from the plain refill's (nothing is copied from the decided epoch), no-ops
 // under the same skip word tot[4].  Under L decision lanes
 // (dv_closed_loop_backoff_lanes) trk->k_next = trk->k + L and the ring's clock
 // for the park is trk->k_next - 1: an abort cannot return before epoch k + L.
@@ -630,12 +659,25 @@ struct RefillBackoff {
     uint32_t *cls, *gb, *bw;
     unsigned long long *wpart, *lost;
 };
-void launch_refill_backoff(hipStream_t s, const uint8_t *status, uint32_t n_txn, const uint64_t *pkeys,
-                           const uint8_t *ptypes, const uint8_t *ptables, const uint32_t *ptb, uint32_t pool_n,
-                           uint32_t *cursor, uint32_t n_out, uint64_t acc_cap, uint64_t *okeys, uint8_t *otypes,
-                           uint32_t *otxn, uint8_t *otables, uint32_t *n_acc_dev, uint32_t *tot, const Counters *ctr,
-                           const uint32_t *precs, uint32_t *orecs, uint32_t *otb, const RefillTrack &trk,
-                           const RefillBackoff &bo);
+
+// the closed loop (dv_epoch_run_closed_loop and its TPC-C and lanes forms): the
+// aborted txns of the decided epoch carried first from `in`, capped at n_out,
+// then n_out - C fresh txns of the pool, into `out`.  acc_bound: a bound on the
+// epoch's accesses (the fresh copy's grid size; with bo, nothing is written at
+// or past it).  trk: the tracker's words, or NULL; bo (with trk): the aborted
+// txns go through the back-off ring instead.
+struct RefillReq {
+    DecidedEpoch ep;
+    AccessCols in;
+    RefillPool pool;
+    uint32_t n_out;
+    uint64_t acc_bound;
+    AccessOut out;
+    CarryWs ws;
+    const RefillTrack *trk;
+    const RefillBackoff *bo;
+};
+void launch_refill(hipStream_t s, const RefillReq &q);
 
 // ---- Deneva client batches decoded on the device (dvcc_wire.hip); the
 // per-call words, their layout and the tiles' sizes: dvcc_wire_layout.h

@@ -927,6 +927,36 @@ int carry_bufs(dv_ctx *c, uint32_t nb) {
     return DV_OK;
 }
 
+// Which columns a carried or refilled epoch holds.  old: keys / types / txn
+// ids, with table bytes when `tables`.  tb (the closed loop's epochs in tb
+// form): 4-byte records and txn boundaries (dv_epoch_dev::recs32, txn_begin).
+// The refill writes the tb form -- 4 B per access and 4 per txn -- and, only
+// when the epochs do not take the prefix-kill path (whose tb mode reads
+// nothing else: k_probe_tb probes the prefix, the kill pass the later keys,
+// DESIGN.md 4), also the old one (8 + 1 + 4 B).
+struct LoopForm {
+    bool tb = false, old = true, tables = true;
+};
+// d's columns of form f as a carry or a refill reads them (args: the
+// operation words of a TPC-C epoch) ...
+AccessCols cols_in(const dv_epoch_dev &d, LoopForm f, const uint64_t *args = nullptr) {
+    return {f.old ? d.keys : nullptr, f.old ? d.types : nullptr, f.old && f.tables ? d.tables : nullptr, d.acc_txn,
+            f.tb ? d.recs32 : nullptr, args};
+}
+// ... and as it writes them: a dv_epoch_dev names its buffers through pointers
+// to const, for the engine that reads them
+AccessOut cols_out(const dv_epoch_dev &d, LoopForm f, uint64_t *args = nullptr) {
+    return {f.old ? const_cast<uint64_t *>(d.keys) : nullptr,
+            f.old ? const_cast<uint8_t *>(d.types) : nullptr,
+            f.old ? const_cast<uint32_t *>(d.acc_txn) : nullptr,
+            f.old && f.tables ? const_cast<uint8_t *>(d.tables) : nullptr,
+            f.tb ? const_cast<uint32_t *>(d.recs32) : nullptr,
+            f.tb ? const_cast<uint32_t *>(d.txn_begin) : nullptr,
+            args,
+            const_cast<uint32_t *>(d.n_acc_dev)};
+}
+CarryWs carry_ws(const dv_ctx *c) { return {c->carry_b, c->carry_b + c->carry_nb, c->carry_tot}; }
+
 // the decided epoch's aborted txns into `out` (checked by the callers), the
 // operation words of a TPC-C epoch (args) into out_args; reads the totals back
 int carry_decided(dv_ctx *c, const dv_epoch_dev *ep, uint32_t max_txn, dv_epoch_dev *out, const uint64_t *args,
@@ -934,11 +964,10 @@ int carry_decided(dv_ctx *c, const dv_epoch_dev *ep, uint32_t max_txn, dv_epoch_
     HIPCHK(hipSetDevice(c->cfg.device));
     int r = carry_bufs(c, carry_blocks(ep->n_txn));
     if (r) return r;
-    launch_carry(c->stream, c->status, c->rs, c->re, ep->n_txn, max_txn, ep->keys, ep->types,
-                 ep->tables, const_cast<uint64_t *>(out->keys), const_cast<uint8_t *>(out->types),
-                 const_cast<uint32_t *>(out->acc_txn),
-                 ep->tables ? const_cast<uint8_t *>(out->tables) : nullptr,
-                 c->carry_b, c->carry_b + c->carry_nb, c->carry_tot, args, out_args);
+    LoopForm f;
+    f.tables = ep->tables != nullptr;
+    launch_carry(c->stream, {{c->status, c->rs, c->re, ep->n_txn, nullptr}, cols_in(*ep, f, args), max_txn,
+                             cols_out(*out, f, out_args), carry_ws(c)});
     HIPCHK(hipGetLastError());
     uint32_t tot[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(tot, c->carry_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
@@ -1002,10 +1031,10 @@ int dv_epoch_group_carry(dv_ctx *c, const dv_epoch_dev *homes, uint32_t n_homes,
         dv_epoch_dev &o = outs[e];
         launch_txn_ranges(c->stream, h.acc_txn, h.n_acc, h.n_txn, tbs, tbe);
         // the commit bytes of this rank's txns of epoch e: 1 committed (== ST_COMMIT), 0 aborted
-        launch_carry(c->stream, d_commit + (size_t)e * txns_per_rank, tbs, tbe, h.n_txn, max_txn, h.keys, h.types,
-                     h.tables, const_cast<uint64_t *>(o.keys), const_cast<uint8_t *>(o.types),
-                     const_cast<uint32_t *>(o.acc_txn), h.tables ? const_cast<uint8_t *>(o.tables) : nullptr,
-                     c->carry_b, c->carry_b + c->carry_nb, c->gc_tot + 3 * e);
+        LoopForm f;
+        f.tables = h.tables != nullptr;
+        launch_carry(c->stream, {{d_commit + (size_t)e * txns_per_rank, tbs, tbe, h.n_txn, nullptr}, cols_in(h, f),
+                                 max_txn, cols_out(o, f), {c->carry_b, c->carry_b + c->carry_nb, c->gc_tot + 3 * e}});
     }
     HIPCHK(hipGetLastError());
     uint32_t tot[3 * kMaxGroupBatches];
@@ -2145,7 +2174,7 @@ int small_enqueue(dv_ctx *c, const dv_epoch_dev *ep) {
 // the kill (run_part); epoch groups (route) vote on the decider's outcome
 // instead, and hand their 32-bit rows over as the 4-byte records.
 bool tb_epoch(const dv_ctx *c, const dv_epoch_dev *ep) {
-    // (a device-side access count: the closed loop's tb-form epochs, loop_tb)
+    // (a device-side access count: the closed loop's tb-form epochs, loop_form)
     return prefix_applies(c, ep) && ep->txn_begin && (!ep->n_acc_dev || ep->recs32) && !ep->tables &&
            (!c->keys32 || ep->recs32) && (!c->rep_P || c->route) && (ep->keys || ep->recs32);
 }
@@ -2493,12 +2522,13 @@ int pipe_redo(dv_ctx *c) {
 
 // Pipelined epochs: epoch k+1 is queued (gated on epoch k) before epoch k
 // is read back.  pipelined(k): epoch k can be queued that way; enqueue(k):
-// queues its decision (the clear honours clear_gate / mir_pending); run(k,
-// st): runs it synchronously (an epoch that cannot be pipelined, or one to
-// redo after a halt).
-template <class Commit, class Pipelined, class Enqueue, class Run>
+// queues its decision (the clear honours clear_gate / mir_pending); after(k):
+// queues what follows its execution (a closed loop's refill; a no-op when the
+// epoch halted); run(k, st): runs it synchronously, with what follows it (an
+// epoch that cannot be pipelined, or one to redo after a halt).
+template <class Commit, class Pipelined, class Enqueue, class After, class Run>
 int run_batch(dv_ctx *c, uint32_t n, dv_stats *sts, Commit &&commit_of, Pipelined &&pipelined, Enqueue &&enqueue,
-              Run &&run) {
+              After &&after, Run &&run) {
     EpochSnap snap[2];
     int64_t pend = -1;  // the epoch queued but not yet read back
     auto stats_of = [&](uint32_t k) { return sts ? &sts[k] : nullptr; };
@@ -2537,6 +2567,7 @@ int run_batch(dv_ctx *c, uint32_t n, dv_stats *sts, Commit &&commit_of, Pipeline
         const bool defer = k + 1 < n && pipelined(k + 1);
         int r = pipe_enqueue(c, [&] { return enqueue(k); }, commit_of(k), pend >= 0, (int)(k & 1), snap[k & 1],
                              defer);
+        if (!r) r = after(k);
         if (r) {
             (void)hipStreamSynchronize(c->stream);
             if (pend >= 0) {  // (its read-back, for the statistics; the error is returned either way)
@@ -2583,6 +2614,7 @@ int dv_epoch_run_device_batch(dv_ctx *c, const dv_epoch_dev *eps, uint32_t n, ui
             if (prefix_applies(c, &eps[k])) return run_prefix_epoch(c, &eps[k]);
             return graph_decide(c, &eps[k], nullptr, [&] { return small_enqueue(c, &eps[k]); });
         },
+        [](uint32_t) { return 0; },
         [&](uint32_t k, dv_stats *st) { return dv_epoch_run_device(c, &eps[k], commit_of(k), nullptr, st); });
 }
 
@@ -2609,6 +2641,7 @@ int dv_tpcc_epoch_run_device_batch(dv_ctx *c, const dv_epoch_dev *eps, const uin
                 return r;
             });
         },
+        [](uint32_t) { return 0; },
         [&](uint32_t k, dv_stats *st) {
             return dv_tpcc_epoch_run_device(c, &eps[k], d_args[k], commit_of(k), oid_of(k), st);
         });
@@ -3090,18 +3123,13 @@ int dv_tpcc_epoch_run_device_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
 
 namespace {
 
-// The closed loop's epochs in tb form: every buffer carries 4-byte records and
-// txn boundaries (dv_epoch_dev::recs32, txn_begin), the pool records, and no
-// table bytes.  The refill then writes that form -- 4 B per access and 4 per
-// txn -- and, only when the epochs do not take the prefix-kill path (whose tb
-// mode reads nothing else: k_probe_tb probes the prefix, the kill pass the
-// later keys), also keys / types / txn ids (8 + 1 + 4 B).
-struct LoopForm {
-    bool tb = false, old = true;
-};
+// The form of a closed loop's epochs (LoopForm): the tb form when every buffer
+// carries 4-byte records and txn boundaries, the pool records, and no table
+// bytes
 LoopForm loop_form(const dv_ctx *c, const dv_epoch_dev *pool, const dv_epoch_dev *bufs, uint32_t n_bufs,
                    uint32_t n_txn) {
     LoopForm f;
+    f.tables = pool->tables != nullptr;
     if (std::getenv("DVCC_LOOP_NO_TB") || !pool->recs32 || pool->tables) return f;
     for (uint32_t b = 0; b < n_bufs; b++)
         if (!bufs[b].recs32 || !bufs[b].txn_begin) return f;
@@ -3113,32 +3141,31 @@ LoopForm loop_form(const dv_ctx *c, const dv_epoch_dev *pool, const dv_epoch_dev
     return f;
 }
 
-// the closed loop's next epoch (launch_refill) into `out`: prev's aborted txns
-// (prev: the epoch the context decided last, prev_buf: its buffer; NULL: none,
-// all fresh), then fresh ones from the pool, in the forms f names
-void enqueue_refill(dv_ctx *c, const dv_epoch_dev *prev, const dv_epoch_dev *prev_buf, const dv_epoch_dev *pool,
-                    const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_out, const dv_epoch_dev &out,
-                    LoopForm f = {}, const RefillTrack *trk = nullptr, const RefillBackoff *bo = nullptr) {
-    if (bo) {  // (the back-off chain: nothing is copied from prev)
-        launch_refill_backoff(c->stream, c->status, prev ? prev->n_txn : 0u, pool->keys, pool->types, pool->tables,
-                              pool_begin, pool->n_txn, cursor, n_out, (uint64_t)n_out * pool->max_txn_acc,
-                              f.old ? const_cast<uint64_t *>(out.keys) : nullptr, const_cast<uint8_t *>(out.types),
-                              const_cast<uint32_t *>(out.acc_txn), const_cast<uint8_t *>(out.tables),
-                              const_cast<uint32_t *>(out.n_acc_dev), c->carry_tot, prev ? c->ctr : nullptr,
-                              f.tb ? pool->recs32 : nullptr, f.tb ? const_cast<uint32_t *>(out.recs32) : nullptr,
-                              f.tb ? const_cast<uint32_t *>(out.txn_begin) : nullptr, *trk, *bo);
-        return;
-    }
-    launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u,
-                  prev && f.old ? prev->keys : nullptr, prev && f.old ? prev->types : nullptr,
-                  prev && f.old ? prev->tables : nullptr, pool->keys, pool->types, pool->tables, pool->acc_txn,
-                  pool_begin, pool->n_txn, cursor, n_out, (uint64_t)n_out * pool->max_txn_acc,
-                  f.old ? const_cast<uint64_t *>(out.keys) : nullptr, const_cast<uint8_t *>(out.types),
-                  const_cast<uint32_t *>(out.acc_txn), const_cast<uint8_t *>(out.tables),
-                  const_cast<uint32_t *>(out.n_acc_dev), c->carry_b, c->carry_b + c->carry_nb, c->carry_tot,
-                  prev ? c->ctr : nullptr, f.tb && prev_buf ? prev_buf->recs32 : nullptr,
-                  f.tb ? pool->recs32 : nullptr, f.tb ? const_cast<uint32_t *>(out.recs32) : nullptr,
-                  f.tb ? const_cast<uint32_t *>(out.txn_begin) : nullptr, nullptr, nullptr, nullptr, trk);
+// What a closed loop's refills share: the pool (pool_args: a TPC-C pool's
+// operation words), the epochs' size and their access bound
+RefillReq loop_refill(const dv_epoch_dev *pool, const uint64_t *pool_args, const uint32_t *pool_begin,
+                      uint32_t *cursor, uint32_t n_txn, uint64_t bound, LoopForm f) {
+    RefillReq q = {};
+    q.pool = {cols_in(*pool, f, pool_args), pool_begin, pool->n_txn, cursor};
+    q.n_out = n_txn;
+    q.acc_bound = bound;
+    return q;
+}
+// the closed loop's next epoch (launch_refill) queued on c: the aborted txns of
+// the epoch c decided last (prev: its buffer; NULL: none, all fresh), then
+// fresh ones from the pool, into `out` in the forms f names; *_args: a TPC-C
+// loop's operation words
+int enqueue_refill(dv_ctx *c, RefillReq q, LoopForm f, const dv_epoch_dev *prev, const dv_epoch_dev &out,
+                   const RefillTrack *trk, const RefillBackoff *bo, const uint64_t *prev_args = nullptr,
+                   uint64_t *out_args = nullptr) {
+    q.ep = {c->status, c->rs, c->re, prev ? q.n_out : 0u, prev ? c->ctr : nullptr};
+    if (prev) q.in = cols_in(*prev, f, prev_args);
+    q.out = cols_out(out, f, out_args);
+    q.ws = carry_ws(c);
+    q.trk = trk;
+    q.bo = bo;
+    launch_refill(c->stream, q);
+    return hip_fail(hipGetLastError(), "refill");
 }
 
 // The loop tracker (dv_closed_loop_track) of context t for one refill: behind
@@ -3231,6 +3258,38 @@ int track_check(const dv_ctx *t, uint32_t n_bufs, uint32_t n_epochs) {
     return DV_OK;
 }
 
+// What every closed-loop entry asks of its call: the pool and the loop's
+// n_bufs buffers complete (tables: the workload needs table bytes), epochs of
+// n_txn txns within the pool, the buffers (buf_cap accesses each) and the
+// context, and an attached tracker (t's) with room for n_epochs.  *bound: an
+// epoch's access bound.
+int loop_check(const dv_ctx *t, const dv_epoch_dev *pool, const uint32_t *pool_begin, const uint32_t *cursor,
+               uint32_t n_txn, const dv_epoch_dev *bufs, uint32_t n_bufs, uint64_t buf_cap, uint32_t n_epochs,
+               bool tables, uint64_t *bound) {
+    if (!pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
+    *bound = (uint64_t)n_txn * pool->max_txn_acc;
+    if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > t->cfg.max_txn || *bound > buf_cap ||
+        *bound > t->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn || (tables && !pool->tables))
+        return DV_ERR_ARG;
+    for (uint32_t b = 0; b < n_bufs; b++)
+        if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].n_acc_dev ||
+            (pool->tables && !bufs[b].tables))
+            return DV_ERR_ARG;
+    return track_check(t, n_bufs, n_epochs);
+}
+// a loop's epoch in buffer buf: n_txn txns, its access count on the device
+dv_epoch_dev loop_desc(const dv_epoch_dev &buf, LoopForm form, const dv_epoch_dev *pool, uint32_t n_txn,
+                       uint64_t bound) {
+    dv_epoch_dev d = buf;
+    if (form.old) d.txn_begin = d.recs32 = nullptr;  // (the engine reads the old form)
+    if (!pool->tables) d.tables = nullptr;
+    d.n_txn = n_txn;
+    d.n_acc = bound;
+    d.max_txn_acc = pool->max_txn_acc;
+    d.ts = nullptr;  // (sequence order: carried txns first keep their priority)
+    return d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3239,116 +3298,52 @@ int dv_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uint32_t
                              uint32_t n_txn, dv_epoch_dev *bufs, uint64_t buf_cap, uint32_t n_epochs,
                              int resume, uint8_t *const *d_commits, dv_stats *sts) {
     KProfScope kps_(c);
-    if (!c || !pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
+    if (!c) return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
     if (c->cfg.cc_alg == DV_CALVIN || c->cfg.workload != DV_YCSB || c->comm) return DV_ERR_STATE;
     if (c->bo.on && c->bo.lanes != 1) return DV_ERR_STATE;  // (a ring attached for the lanes loop)
-    const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
-    if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
-        bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn)
-        return DV_ERR_ARG;
-    for (int b = 0; b < 2; b++)
-        if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].n_acc_dev ||
-            (pool->tables && !bufs[b].tables))
-            return DV_ERR_ARG;
-    if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
+    uint64_t bound = 0;
+    int r = loop_check(c, pool, pool_begin, cursor, n_txn, bufs, 2, buf_cap, n_epochs, false, &bound);
+    if (r) return r;
     HIPCHK(hipSetDevice(c->cfg.device));
-    int r = carry_bufs(c, carry_blocks(n_txn));
+    r = carry_bufs(c, carry_blocks(n_txn));
     if (!r) r = backoff_bufs(c, carry_blocks(n_txn), c->bo.on);
     if (r) return r;
     const LoopForm form = loop_form(c, pool, bufs, 2, n_txn);
+    const RefillReq req = loop_refill(pool, nullptr, pool_begin, cursor, n_txn, bound, form);
     RefillTrack tw;
     RefillBackoff bw;
-    // epoch k's descriptor: buffer k & 1, its access count on the device
-    auto desc = [&](uint32_t k) {
-        dv_epoch_dev d = bufs[k & 1];
-        if (form.old) d.txn_begin = d.recs32 = nullptr;  // (the engine reads the old form)
-        d.tables = pool->tables ? bufs[k & 1].tables : nullptr;
-        d.n_txn = n_txn;
-        d.n_acc = bound;
-        d.max_txn_acc = pool->max_txn_acc;
-        d.ts = nullptr;  // (sequence order: carried txns first keep their priority)
-        return d;
-    };
+    // epoch k's descriptor: buffer k & 1
+    auto desc = [&](uint32_t k) { return loop_desc(bufs[k & 1], form, pool, n_txn, bound); };
     auto commit_of = [&](uint32_t k) { return d_commits ? d_commits[k] : nullptr; };
-    auto stats_of = [&](uint32_t k) { return sts ? &sts[k] : nullptr; };
-    auto fail = [&](int e) {
-        c->mir_pending = false;
-        (void)hipStreamSynchronize(c->stream);
-        return e;
+    // behind epoch k's execution: epoch k + 1 from epoch k's final statuses (a
+    // no-op when k halted -- run_batch redoes both)
+    auto refill = [&](uint32_t k) {
+        return enqueue_refill(c, req, form, &bufs[k & 1], bufs[(k + 1) & 1],
+                              track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
+                              backoff_at(c, c, k & 1, (k + 1) & 1, &bw));
     };
     if (!resume)
-        enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, bufs[0], form,
-                       track_at(c, false, 0, 0, 0, 0, 1, &tw), backoff_at(c, c, 0, 0, &bw));
+        r = enqueue_refill(c, req, form, nullptr, bufs[0], track_at(c, false, 0, 0, 0, 0, 1, &tw),
+                           backoff_at(c, c, 0, 0, &bw));
     const dv_epoch_dev d0 = desc(0);
     const bool pipelined = prefix_applies(c, &d0) && !timing(c) && !ktiming(c) && !c->rep_P;
-    EpochSnap snap[2];
-    int64_t pend = -1;
-    // epoch k run synchronously, then its refill
-    auto run_one = [&](uint32_t k) {
-        const dv_epoch_dev d = desc(k);
-        int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, stats_of(k));
-        if (!e) {
-            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
-                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
-                           backoff_at(c, c, k & 1, (k + 1) & 1, &bw));
-            e = hip_fail(hipGetLastError(), "refill");
-        }
-        return e;
-    };
-    for (uint32_t k = 0; k < n_epochs; k++) {
-        if (!pipelined) {
-            r = run_one(k);
-            if (r) return fail(r);
-            continue;
-        }
-        const dv_epoch_dev d = desc(k);
-        r = pipe_enqueue(c, [&] { return run_prefix_epoch(c, &d); }, commit_of(k), pend >= 0, (int)(k & 1),
-                         snap[k & 1], k + 1 < n_epochs);
-        if (!r) {
-            // behind the execution: epoch k + 1 from epoch k's final statuses (a
-            // no-op when k halted -- the host redoes both below)
-            enqueue_refill(c, &d, &bufs[k & 1], pool, pool_begin, cursor, n_txn, bufs[(k + 1) & 1], form,
-                           track_at(c, true, k, k + 1, k & 1, (k + 1) & 1, 1, &tw),
-                           backoff_at(c, c, k & 1, (k + 1) & 1, &bw));
-            r = hip_fail(hipGetLastError(), "refill");
-        }
-        if (r) {
-            (void)hipStreamSynchronize(c->stream);
-            if (pend >= 0) {
-                bool halted = false;
-                (void)pipe_complete(c, snap[pend & 1], stats_of((uint32_t)pend), &halted);
-            }
-            return fail(r);
-        }
-        if (pend >= 0) {
-            bool halted = false;
-            r = pipe_complete(c, snap[pend & 1], stats_of((uint32_t)pend), &halted);
-            if (r) return fail(r);
-            if (halted) {
-                // epoch pend halted: epoch k started halted and neither refill
-                // ran.  Decide pend again synchronously, refill from it, and
-                // queue epoch k again.
-                c->mir_pending = false;
-                r = pipe_redo(c);
-                if (!r) r = run_one((uint32_t)pend);
-                if (r) return fail(r);
-                pend = -1;
-                k--;  // (k = pend + 1 again)
-                continue;
-            }
-        }
-        pend = k;
-    }
-    if (pend >= 0) {
-        bool halted = false;
-        r = pipe_complete(c, snap[pend & 1], stats_of((uint32_t)pend), &halted);
-        if (r) return fail(r);
-        if (halted) {
-            r = pipe_redo(c);
-            if (!r) r = run_one((uint32_t)pend);
-            if (r) return fail(r);
-        }
+    if (!r)
+        r = run_batch(
+            c, n_epochs, sts, commit_of, [&](uint32_t) { return pipelined; },
+            [&](uint32_t k) {
+                const dv_epoch_dev d = desc(k);
+                return run_prefix_epoch(c, &d);
+            },
+            refill,
+            [&](uint32_t k, dv_stats *st) {  // (synchronously, then its refill)
+                const dv_epoch_dev d = desc(k);
+                const int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, st);
+                return e ? e : refill(k);
+            });
+    if (r) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
     c->trk.next += c->trk.on ? n_epochs : 0u;
@@ -3367,56 +3362,30 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
                                   uint64_t *const *buf_args, uint64_t buf_cap, uint32_t n_epochs, int resume,
                                   uint8_t *const *d_commits, uint64_t *const *d_oids, dv_stats *sts) {
     KProfScope kps_(c);
-    if (!c || !pool || !pool_args || !pool_begin || !cursor || !bufs || !buf_args || !n_txn ||
-        c->cfg.workload != DV_TPCC)
-        return DV_ERR_ARG;
+    if (!c || !pool_args || !buf_args || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
     if (c->cfg.cc_alg == DV_CALVIN || c->comm || c->bo.on) return DV_ERR_STATE;  // (bo: the YCSB loops only)
-    const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
-    if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c->cfg.max_txn || bound > buf_cap ||
-        bound > c->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn || !pool->tables)
-        return DV_ERR_ARG;
-    for (int b = 0; b < 2; b++)
-        if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].tables || !bufs[b].n_acc_dev ||
-            !buf_args[b])
-            return DV_ERR_ARG;
-    if (track_check(c, 2, n_epochs)) return DV_ERR_ARG;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    int r = carry_bufs(c, carry_blocks(n_txn));
+    uint64_t bound = 0;
+    int r = loop_check(c, pool, pool_begin, cursor, n_txn, bufs, 2, buf_cap, n_epochs, true, &bound);
+    if (!r && (!buf_args[0] || !buf_args[1])) r = DV_ERR_ARG;
     if (r) return r;
-    // epoch k's descriptor: buffer k & 1, its access count on the device
-    auto desc = [&](uint32_t k) {
-        dv_epoch_dev d = bufs[k & 1];
-        d.txn_begin = d.recs32 = nullptr;
-        d.n_txn = n_txn;
-        d.n_acc = bound;
-        d.max_txn_acc = pool->max_txn_acc;
-        d.ts = nullptr;  // (sequence order: carried txns first keep their priority)
-        return d;
-    };
-    // prev's aborted txns (NULL: none; k: its place in this call), then fresh
-    // pool txns, into buffer `into`
-    auto refill = [&](const dv_epoch_dev *prev, const uint64_t *prev_args, int into, uint32_t k) {
-        const dv_epoch_dev &o = bufs[into];
-        RefillTrack tw;
-        launch_refill(c->stream, c->status, c->rs, c->re, prev ? prev->n_txn : 0u, prev ? prev->keys : nullptr,
-                      prev ? prev->types : nullptr, prev ? prev->tables : nullptr, pool->keys, pool->types,
-                      pool->tables, pool->acc_txn, pool_begin, pool->n_txn, cursor, n_txn, bound,
-                      const_cast<uint64_t *>(o.keys), const_cast<uint8_t *>(o.types),
-                      const_cast<uint32_t *>(o.acc_txn), const_cast<uint8_t *>(o.tables),
-                      const_cast<uint32_t *>(o.n_acc_dev), c->carry_b, c->carry_b + c->carry_nb, c->carry_tot,
-                      prev ? c->ctr : nullptr, nullptr, nullptr, nullptr, nullptr, prev_args, pool_args,
-                      buf_args[into],
-                      track_at(c, prev != nullptr, k, prev ? k + 1 : 0u, (uint32_t)(into ^ 1), (uint32_t)into, 1,
-                               &tw));
-        return hip_fail(hipGetLastError(), "refill");
-    };
-    if (!resume) r = refill(nullptr, nullptr, 0, 0);
+    HIPCHK(hipSetDevice(c->cfg.device));
+    r = carry_bufs(c, carry_blocks(n_txn));
+    if (r) return r;
+    const LoopForm form{};
+    const RefillReq req = loop_refill(pool, pool_args, pool_begin, cursor, n_txn, bound, form);
+    RefillTrack tw;
+    if (!resume)
+        r = enqueue_refill(c, req, form, nullptr, bufs[0], track_at(c, false, 0, 0, 1, 0, 1, &tw), nullptr, nullptr,
+                           buf_args[0]);
     for (uint32_t k = 0; !r && k < n_epochs; k++) {
-        const dv_epoch_dev d = desc(k);
-        r = dv_tpcc_epoch_run_device(c, &d, buf_args[k & 1], d_commits ? d_commits[k] : nullptr,
+        const uint32_t ib = k & 1, ob = (k + 1) & 1;
+        const dv_epoch_dev d = loop_desc(bufs[ib], form, pool, n_txn, bound);
+        r = dv_tpcc_epoch_run_device(c, &d, buf_args[ib], d_commits ? d_commits[k] : nullptr,
                                      d_oids ? d_oids[k] : nullptr, sts ? &sts[k] : nullptr);
-        if (!r) r = refill(&d, buf_args[k & 1], (int)((k + 1) & 1), k);
+        if (!r)
+            r = enqueue_refill(c, req, form, &bufs[ib], bufs[ob], track_at(c, true, k, k + 1, ib, ob, 1, &tw),
+                               nullptr, buf_args[ib], buf_args[ob]);
     }
     if (r) {
         (void)hipStreamSynchronize(c->stream);
@@ -3444,25 +3413,16 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     if (n_lanes == 1)
         return dv_epoch_run_closed_loop(lanes[0], pool, pool_begin, cursor, n_txn, bufs, buf_cap, n_epochs, resume,
                                         d_commits, sts);
-    if (!pool || !pool_begin || !cursor || !bufs || !n_txn) return DV_ERR_ARG;
     dv_ctx *const c0 = lanes[0];
     KProfScope kps_(c0);  // (DV_FLAG_KERNEL_PROFILE on lanes[0]: every lane's refill launches are timed into it)
     if (c0->cfg.cc_alg == DV_CALVIN || c0->cfg.workload != DV_YCSB) return DV_ERR_STATE;
     // a back-off: lanes[0]'s, attached for this lane count (dv_closed_loop_backoff_lanes)
     if (c0->bo.on && c0->bo.lanes != n_lanes) return DV_ERR_STATE;
-    for (uint32_t l = 1; l < n_lanes; l++)
-        if (lanes[l]->bo.on) return DV_ERR_STATE;
-    const uint64_t bound = (uint64_t)n_txn * pool->max_txn_acc;
-    if (!pool->max_txn_acc || n_txn > pool->n_txn || n_txn > c0->cfg.max_txn || bound > buf_cap ||
-        bound > c0->cfg.max_acc || !pool->keys || !pool->types || !pool->acc_txn)
-        return DV_ERR_ARG;
-    for (uint32_t b = 0; b < 2 * n_lanes; b++)
-        if (!bufs[b].keys || !bufs[b].types || !bufs[b].acc_txn || !bufs[b].n_acc_dev ||
-            (pool->tables && !bufs[b].tables))
-            return DV_ERR_ARG;
     for (uint32_t l = 0; l < n_lanes; l++)
-        if (lanes[l]->comm) return DV_ERR_STATE;
-    if (track_check(c0, 2 * n_lanes, n_epochs)) return DV_ERR_ARG;
+        if ((l && lanes[l]->bo.on) || lanes[l]->comm) return DV_ERR_STATE;
+    uint64_t bound = 0;
+    r = loop_check(c0, pool, pool_begin, cursor, n_txn, bufs, 2 * n_lanes, buf_cap, n_epochs, false, &bound);
+    if (r) return r;
     HIPCHK(hipSetDevice(c0->cfg.device));
     for (uint32_t l = 0; l < n_lanes; l++) {
         r = carry_bufs(lanes[l], carry_blocks(n_txn));
@@ -3470,35 +3430,29 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
         if (r) return r;
     }
     const LoopForm form = loop_form(c0, pool, bufs, 2 * n_lanes, n_txn);
+    const RefillReq req = loop_refill(pool, nullptr, pool_begin, cursor, n_txn, bound, form);
     // lane l's j-th epoch of this call (global k = j * L + l) sits in buffer
     // 2l + (j & 1); its refill writes 2l + ((j + 1) & 1)
     auto buf_i = [&](uint32_t k, uint32_t ahead) { return 2 * (k % n_lanes) + (((k / n_lanes) + ahead) & 1); };
-    auto buf_of = [&](uint32_t k, uint32_t ahead) { return &bufs[buf_i(k, ahead)]; };
     // (the tracker and the back-off are lanes[0]'s, shared: the refills run in epoch order)
     RefillTrack tw;
     RefillBackoff bw;
-    auto track_of = [&](uint32_t k) {
-        return track_at(c0, true, k, k + n_lanes, buf_i(k, 0), buf_i(k, 1), n_lanes, &tw);
-    };
-    auto backoff_of = [&](dv_ctx *c, uint32_t k) { return backoff_at(c0, c, buf_i(k, 0), buf_i(k, 1), &bw); };
-    auto desc = [&](uint32_t k) {
-        dv_epoch_dev d = *buf_of(k, 0);
-        if (form.old) d.txn_begin = d.recs32 = nullptr;  // (the engine reads the old form)
-        d.tables = pool->tables ? d.tables : nullptr;
-        d.n_txn = n_txn;
-        d.n_acc = bound;
-        d.max_txn_acc = pool->max_txn_acc;
-        d.ts = nullptr;
-        return d;
-    };
+    auto desc = [&](uint32_t k) { return loop_desc(bufs[buf_i(k, 0)], form, pool, n_txn, bound); };
     auto commit_of = [&](uint32_t k) { return d_commits ? d_commits[k] : nullptr; };
+    // behind epoch k's execution on its lane c (a no-op when k halted)
+    auto refill = [&](dv_ctx *c, uint32_t k) {
+        const uint32_t ib = buf_i(k, 0), ob = buf_i(k, 1);
+        return enqueue_refill(c, req, form, &bufs[ib], bufs[ob],
+                              track_at(c0, true, k, k + n_lanes, ib, ob, n_lanes, &tw),
+                              backoff_at(c0, c, ib, ob, &bw));
+    };
     if (!resume)  // each lane's first epoch: fresh txns (and what an attached ring releases), in lane order
         for (uint32_t l = 0; l < n_lanes; l++) {
             dv_ctx *c = lanes[l];
-            enqueue_refill(c, nullptr, nullptr, pool, pool_begin, cursor, n_txn, *buf_of(l, 0), form,
-                           track_at(c0, false, 0, l, 0, buf_i(l, 0), n_lanes, &tw),
-                           backoff_at(c0, c, buf_i(l, 0), buf_i(l, 0), &bw));
-            HIPCHK(hipGetLastError());
+            r = enqueue_refill(c, req, form, nullptr, bufs[buf_i(l, 0)],
+                               track_at(c0, false, 0, l, 0, buf_i(l, 0), n_lanes, &tw),
+                               backoff_at(c0, c, buf_i(l, 0), buf_i(l, 0), &bw));
+            if (r) return r;
             HIPCHK(hipStreamSynchronize(c->stream));
         }
     const dv_epoch_dev d0 = desc(0);
@@ -3510,22 +3464,13 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
             const int e = run_prefix_epoch(c, &d);
             return e ? e : tail();
         },
-        [&](dv_ctx *c, uint32_t k) {  // (behind the execution; a no-op when k halted)
-            const dv_epoch_dev d = desc(k);
-            enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form, track_of(k),
-                           backoff_of(c, k));
-            return hip_fail(hipGetLastError(), "refill");
-        },
+        refill,
         [&](uint32_t k, dv_stats *st) {  // (synchronous, refill included: the next refill, on
                                          // another lane, draws from the cursor after it)
             dv_ctx *c = lanes[k % n_lanes];
             const dv_epoch_dev d = desc(k);
             int e = dv_epoch_run_device(c, &d, commit_of(k), nullptr, st);
-            if (!e) {
-                enqueue_refill(c, &d, buf_of(k, 0), pool, pool_begin, cursor, n_txn, *buf_of(k, 1), form,
-                               track_of(k), backoff_of(c, k));
-                e = hip_fail(hipGetLastError(), "refill");
-            }
+            if (!e) e = refill(c, k);
             if (!e) e = hip_fail(hipStreamSynchronize(c->stream), "sync");
             return e;
         });

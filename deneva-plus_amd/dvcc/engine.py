@@ -432,7 +432,7 @@ class LoopBackoff:
 
 
 def _loop_tb(pool, bufs):
-    """dv_epoch_run_closed_loop writes the tb form (loop_tb, dvcc_runtime.hip)"""
+    """dv_epoch_run_closed_loop writes the tb form (loop_form, dvcc_runtime.hip)"""
     import os
     return (not os.environ.get("DVCC_LOOP_NO_TB") and getattr(pool, "recs32", None) is not None
             and pool.tables is None and all(b.recs32 is not None for b in bufs))
@@ -901,6 +901,15 @@ class CCEngine:
             track._before(self, n_txn, n_bufs)
         return track
 
+    @staticmethod
+    def _loop_state(pool, cursor, n_epochs):
+        """a loop call's pool cursor (a zero device word when None) and its
+        stats array"""
+        import torch
+        if cursor is None:
+            cursor = torch.zeros(1, dtype=torch.int32, device=pool.keys.device)
+        return cursor, (L.Stats * max(1, n_epochs))()
+
     def closed_loop(self, pool, pool_begin, n_txn, n_epochs, cursor=None, bufs=None, d_commits=None,
                     resume=False, track=None):
         """The closed loop on the device (dv_epoch_run_closed_loop): n_epochs
@@ -912,24 +921,17 @@ class CCEngine:
         attached to this engine (identity through the loop: its commit log,
         retry histogram and totals).  Returns (stats list, bufs, cursor); the
         next epoch is in bufs.epoch(n_epochs & 1)."""
-        import torch
         track = self._tracked(track, n_txn, 2)
-        dev = pool.keys.device
-        if cursor is None:
-            cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        cursor, sts = self._loop_state(pool, cursor, n_epochs)
         if bufs is None:
-            bufs = ClosedLoopBufs(n_txn * pool.max_txn_acc, pool.tables is not None, dev, n_txn=n_txn)
+            bufs = ClosedLoopBufs(n_txn * pool.max_txn_acc, pool.tables is not None, pool.keys.device, n_txn=n_txn)
         bufs.tb = _loop_tb(pool, [bufs])
         arr = (L.EpochDev * 2)(*[bufs.desc(b) for b in range(2)])
-        if d_commits is None or not isinstance(d_commits, (list, tuple)):
-            d_commits = [d_commits] * n_epochs
-        cps = (ctypes.c_void_p * max(1, n_epochs))(*[(int(t.data_ptr()) if t is not None else None)
-                                                     for t in d_commits])
-        sts = (L.Stats * max(1, n_epochs))()
         self._after_torch()
         L.check(L.lib().dv_epoch_run_closed_loop(self._ctx, ctypes.byref(pool.desc()), _ptr(pool_begin),
                                                  _ptr(cursor), n_txn, arr, bufs.cap, n_epochs, int(resume),
-                                                 cps, sts), "dv_epoch_run_closed_loop")
+                                                 _commit_ptrs(d_commits, len(sts)), sts),
+                "dv_epoch_run_closed_loop")
         if track is not None:
             track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor
@@ -945,31 +947,24 @@ class CCEngine:
         L - 1 + min(2^(a-1), D) epochs).  Returns (stats
         list, bufs, cursor); resume needs the previous call's n_epochs to be a
         multiple of 2 L."""
-        import torch
         ctxs = [self] + list(lanes)
         nl = len(ctxs)
         track = self._tracked(track, n_txn, 2 * nl)
-        dev = pool.keys.device
-        if cursor is None:
-            cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        cursor, sts = self._loop_state(pool, cursor, n_epochs)
         if bufs is None:
-            bufs = [ClosedLoopBufs(n_txn * pool.max_txn_acc, pool.tables is not None, dev, n_txn=n_txn)
+            bufs = [ClosedLoopBufs(n_txn * pool.max_txn_acc, pool.tables is not None, pool.keys.device, n_txn=n_txn)
                     for _ in range(nl)]
         tb = _loop_tb(pool, bufs)
         for b in bufs:
             b.tb = tb
         arr = (L.EpochDev * (2 * nl))(*[b.desc(i) for b in bufs for i in range(2)])
-        if d_commits is None or not isinstance(d_commits, (list, tuple)):
-            d_commits = [d_commits] * n_epochs
-        cps = (ctypes.c_void_p * max(1, n_epochs))(*[(int(t.data_ptr()) if t is not None else None)
-                                                     for t in d_commits])
-        sts = (L.Stats * max(1, n_epochs))()
         lp = (ctypes.c_void_p * nl)(*[e._ctx.value for e in ctxs])
         for e in ctxs:
             e._after_torch()
         L.check(L.lib().dv_epoch_run_closed_loop_lanes(lp, nl, ctypes.byref(pool.desc()), _ptr(pool_begin),
                                                        _ptr(cursor), n_txn, arr, bufs[0].cap, n_epochs,
-                                                       int(resume), cps, sts), "dv_epoch_run_closed_loop_lanes")
+                                                       int(resume), _commit_ptrs(d_commits, len(sts)), sts),
+                "dv_epoch_run_closed_loop_lanes")
         if track is not None:
             track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor

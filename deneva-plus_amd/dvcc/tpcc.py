@@ -181,18 +181,14 @@ class TpccEngine(CCEngine):
         one for all, or None.  track: a LoopTrack attached to this engine.
         Returns (stats list, bufs, cursor); the next epoch is in
         bufs.epoch(n_epochs & 1)."""
-        import torch
         track = self._tracked(track, n_txn, 2)
-        dev = pool.keys.device
-        if cursor is None:
-            cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        cursor, sts = self._loop_state(pool, cursor, n_epochs)
         if bufs is None:
-            bufs = TpccLoopBufs(n_txn * pool.max_txn_acc, dev)
+            bufs = TpccLoopBufs(n_txn * pool.max_txn_acc, pool.keys.device)
         arr = (L.EpochDev * 2)(*[bufs.desc(b) for b in range(2)])
         bargs = getattr(bufs, "args", None) or [None, None]
         aps = (ctypes.c_void_p * 2)(*[(int(t.data_ptr()) if t is not None else None) for t in bargs])
-        n = max(1, n_epochs)
-        sts = (L.Stats * n)()
+        n = len(sts)
         self._after_torch()
         L.check(L.lib().dv_tpcc_epoch_run_closed_loop(self._ctx, ctypes.byref(pool.desc()), _ptr(pool_args),
                                                       _ptr(pool_begin), _ptr(cursor), n_txn, arr, aps, bufs.cap,

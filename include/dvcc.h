@@ -184,7 +184,7 @@ typedef struct dv_epoch_dev {
                                 (dv_epoch_run_part, dv_epoch_group_run) take
                                 NULL only (DV_ERR_ARG voted on every rank). */
     const uint32_t *n_acc_dev; /* (device) the real access count when it is
-                                known only on the device (dv_epoch_refill):
+                                known only on the device (the closed loops):
                                 n_acc is then an upper bound, and arrays may
                                 hold anything past the real count.  NULL: n_acc
                                 is exact.  Single-GPU entry points, NO_WAIT /

@@ -202,17 +202,20 @@ def test_device_closed_loop(cc, prefix):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cc", [dvcc.NO_WAIT, dvcc.OCC])
-def test_device_closed_loop_halts_and_resume(cc):
+@pytest.mark.parametrize("per_call", [1, 2, 3])
+def test_device_closed_loop_halts_and_resume(cc, per_call):
     """asynchronous launches forced to yield (every epoch halts and is decided
     again before its successor is rebuilt), and a loop continued over three
-    calls (resume) -- the same epochs as one host loop"""
+    calls (resume) -- the same epochs as one host loop.  One epoch per call:
+    the halted epoch is the call's last, nothing queued behind it; two: a
+    gated successor behind it; three: the epoch after a redone pair too"""
     rows, N = 1 << 13, 3000
     pool = _pool(rows, 4000, 12, R=12)
     eng = CCEngine(cc, N, N * 12)
     eng.set_prefix(500)
     eng.set_async_limits(1, 0)
     eng.load_ycsb_partition(rows)
-    _check_loop(eng, cc, rows, pool, N, 3, calls=3)
+    _check_loop(eng, cc, rows, pool, N, per_call, calls=3)
     eng.close()
 
 
