@@ -89,11 +89,14 @@ def structural_constants():
     """kTile (the synchronous pass's tile of 32-bit elements and of 64-bit
     ones), kAsyncCap, the tail capacities, kBlock / kCarryTpb, kHotRows and
     the Bloom filter's bits, and the partitioned path's kXTile (a tile of
-    landed accesses), kIlTxns / kIlOwn (k_il_move_tb's tile of txns and its
-    LDS index), kMaxPos (the longest txn) and kRouteBlocks, from csrc/."""
+    landed accesses), kOwnerTile (the owner split's tile of home accesses:
+    dvcc_internal.h's kTile, the radix kernels'), kIlTxns / kIlOwn
+    (k_il_move_tb's tile of txns and its LDS index), kMaxPos (the longest txn)
+    and kRouteBlocks, from csrc/."""
     rounds, internal, prefix = _src("dvcc_rounds.hip"), _src("dvcc_internal.h"), _src("dvcc_prefix.hip")
     comm = _src("dvcc_comm.hip")
     assert re.search(r"constexpr\s+uint32_t\s+kXTile\s*=\s*kBlock\s*\*\s*kXIPT\s*;", comm)
+    assert re.search(r"constexpr\s+int\s+kTile\s*=\s*kBlock\s*\*\s*kIPT\s*;", internal)
     il = re.search(r"constexpr\s+uint32_t\s+kIlTxns\s*=\s*(\d+)\s*,\s*kIlOwn\s*=\s*(\d+)\s*;", comm)
     max_pos = re.search(r"constexpr\s+uint32_t\s+kMaxPos\s*=\s*1u\s*<<\s*(\d+)\s*;", internal)
     t32 = int(re.search(r"kThreads\s*=\s*sizeof\(EIn\)\s*==\s*4\s*\?\s*(\d+)", rounds).group(1))
@@ -112,6 +115,7 @@ def structural_constants():
         kBloomBits=1 << _define(prefix, "DVCC_BLOOM_LOG"),
         kRoundLog=_const(internal, "kRoundLog"),
         kXTile=_const(internal, "kBlock") * _const(comm, "kXIPT"),
+        kOwnerTile=_const(internal, "kBlock") * _const(internal, "kIPT"),
         kIlTxns=int(il.group(1)),
         kIlOwn=int(il.group(2)),
         kMaxPos=1 << int(max_pos.group(1)),

@@ -775,6 +775,8 @@ def cases():
 
 CASES = cases()
 SWEEPS = ("cust", "stock")  # family 7, the only large one: built once, by the tests that run it
+# the families that also run partitioned at world 2 (test_adversarial_tpcc_part_gpu.py says why not name_*)
+PART_CASES = [n for n in CASES if not n.startswith("name_")]
 
 
 @functools.lru_cache(maxsize=None)
@@ -785,3 +787,326 @@ def built(name):
 @functools.lru_cache(maxsize=2)
 def built_sweep(kind):
     return second_sweep(kind)
+
+
+# ---- family 8: ragged ladder, partitioned(world, slots, own).  The TPC-C
+# counterpart of adversarial.ragged_ladder for dv_tpcc_epoch_run_part's list
+# protocol: one warehouse per partition (Ctx(num_wh=world), warehouse w on
+# partition (w - 1) % world).  `slots` lists the epoch's sequence slots: EMPTY,
+# ONE (a single private access) or a pad count p (a ladder txn: the k-th writes
+# link rows L_k and L_k+1, then p private accesses; 2 + p <= 33, the longest
+# NewOrder).  All accesses are writes with an operation word:
+#   link L_k   CUSTOMER (k // m + 1) of district LINK_DIST in link warehouse
+#              k % m, OP_PAY_CUST: consecutive links sit on different
+#              partitions, so an odd ladder txn loses on L_k's partition while
+#              its other records live elsewhere
+#   private    used once in the epoch: a CUSTOMER payment (districts 1..9) or,
+#              every fifth of a warehouse, a STOCK write; the i-th private
+#              access goes to warehouse
+#                spread     i % world + 1
+#                part0      1
+#                skip_last  i % (world - 1) + 1
+#              (adversarial.OWNERSHIPS for the private accesses).  Under
+#              skip_last at world >= 3 links and districts keep off the last
+#              warehouse too (that partition receives no record at all); else
+#              they use every warehouse
+#   district   a handful of txns swap their first private access for a
+#              NewOrder's DISTRICT access (a_nodist): three even ladder txns on
+#              districts D0, D1, D2, three odd ones on D0, D0, D3 and one ONE
+#              slot on D4, spread over the epoch and over the warehouses.
+# Operands: payments 2^i where the epoch has at most 40 of them, i + 1 + salt
+# otherwise; stock quantities 1 + (i + salt) % 10; link payments 2^20 + index.
+# The rule (asserted by the builder): private rows are used once and a district
+# has at most one writer outside the odd ladder txns, so under NO_WAIT /
+# WAIT_DIE / OCC the ladder decides as adversarial's family 1 -- the k-th
+# ladder txn commits iff k is even (an odd one meets the lock / the committed
+# write on L_k; it leaves nothing behind, so its district access never blocks a
+# later txn) -- and every other txn commits.  CALVIN: all commit; D0's three
+# NewOrders take D_NEXT_O_ID + 1, + 2, + 3 in sequence order.
+EMPTY, ONE = A.EMPTY, A.ONE
+LINK_DIST = 10
+MAX_TXN_ACC = 33
+
+
+@functools.lru_cache(maxsize=None)
+def ctx_world(world):
+    return Ctx(num_wh=world)
+
+
+def wh_to_part(w, world):
+    return (w - 1) % world
+
+
+def owner_bytes(cx, e, world):
+    """the partition of every access, from the warehouse in its key
+    (tpcc_helper.cpp:19-43 and wh_to_part); an ITEM read goes with the STOCK
+    write that follows it (the supplying warehouse, as tpcc_gen.cpp has it)"""
+    k, t = e.keys.astype(np.int64), e.tables
+    cpd, mi = cx.kw["cust_per_dist"], cx.kw["max_items"]
+    w = np.zeros(e.n_acc, np.int64)
+    w[t == T_WH] = k[t == T_WH]
+    w[t == T_DIST] = (k[t == T_DIST] - 1) // 10
+    w[t == T_CUST] = ((k[t == T_CUST] - 1) // cpd - 1) // 10
+    w[t == T_STOCK] = (k[t == T_STOCK] - 1) // mi
+    assert not (t == T_CLAST).any(), "a last-name key does not name its warehouse"
+    item = np.flatnonzero(t == T_ITEM)
+    if item.size:
+        assert item[-1] + 1 < e.n_acc and (t[item + 1] == T_STOCK).all() and (e.acc_txn()[item] == e.acc_txn()[item + 1]).all()
+        w[item] = w[item + 1]
+    assert e.n_acc == 0 or (w.min() >= 1 and w.max() <= cx.kw["num_wh"])
+    return wh_to_part(w, world).astype(np.uint8)
+
+
+def _spaced(c, m):
+    """up to m of c, evenly spaced, first and last among them"""
+    if len(c) <= m:
+        return list(c)
+    return [c[i] for i in sorted({round(j * (len(c) - 1) / (m - 1)) for j in range(m)})]
+
+
+def ragged_tpcc_epoch(world, slots, own, salt=0):
+    """(epoch with owner bytes, {cc: commit bytes}, info) -- the comment above"""
+    cx = ctx_world(world)
+    cpd, mi = cx.kw["cust_per_dist"], cx.kw["max_items"]
+    slots = list(slots)
+    lad = [i for i, s in enumerate(slots) if s is not EMPTY and s != ONE]
+    ones = [i for i, s in enumerate(slots) if s is not EMPTY and s == ONE]
+    assert all(2 + slots[i] <= MAX_TXN_ACC for i in lad)
+    L = len(lad)
+    narrow = own == "skip_last" and world >= 3
+    link_wh = list(range(1, world if narrow else world + 1))
+    priv_wh = {"spread": list(range(1, world + 1)), "part0": [1], "skip_last": list(range(1, max(2, world)))}[own]
+    assert len(link_wh) >= 2
+
+    def link(k):
+        c = k // len(link_wh) + 1
+        assert c <= cpd
+        return cx.k_cust(c, LINK_DIST, link_wh[k % len(link_wh)])
+
+    dist = [cx.k_dist(j % 9 + 1, link_wh[j % len(link_wh)]) for j in range(5)]
+    padded = [k for k in range(L) if slots[lad[k]] >= 1]
+    nod = {}  # slot -> district key
+    for k, d in zip(_spaced([k for k in padded if k % 2 == 0], 3), (0, 1, 2)):
+        nod[lad[k]] = dist[d]
+    for k, d in zip(_spaced([k for k in padded if k % 2 == 1], 3), (0, 0, 3)):
+        nod[lad[k]] = dist[d]
+    if ones:
+        nod[ones[len(ones) // 2]] = dist[4]
+    # private accesses, in sequence order
+    n_priv = sum((1 if s == ONE else s) for s in slots if s is not EMPTY) - len(nod)
+    per_wh = {w: 0 for w in priv_wh}
+    priv, n_cust = [], 0
+    for i in range(n_priv):
+        w = priv_wh[i % len(priv_wh)]
+        j = per_wh[w]
+        per_wh[w] += 1
+        if j % 5 == 4:
+            priv.append((T_STOCK, w, j // 5))
+        else:
+            priv.append((T_CUST, w, j - j // 5))
+            n_cust += 1
+    hs = _amounts(n_cust) if n_cust <= 40 else np.arange(n_cust, dtype=np.uint64) + np.uint64(1 + salt)
+    b = _EB()
+    pi = ci = si = 0
+    sum_h = {False: 0, True: 0}  # payments' amounts: of the txns the deciders commit / of the others
+    sum_q, n_q = {False: 0, True: 0}, {False: 0, True: 0}
+    k = 0
+    for i, s in enumerate(slots):
+        if s is EMPTY:
+            b.txn()
+            continue
+        acc, lost = [], False
+        n = 1 if s == ONE else s
+        if s != ONE:
+            lost = k % 2 == 1
+            for j, kk in enumerate((k, k + 1)):
+                h = (1 << 20) + 2 * k + j
+                acc.append(a_pcust(link(kk), h))
+                sum_h[lost] += h
+            k += 1
+        if i in nod:
+            acc.append(a_nodist(nod[i]))
+            n -= 1
+        for _ in range(n):
+            t, w, j = priv[pi]
+            pi += 1
+            if t == T_STOCK:
+                assert j < mi
+                q = 1 + (si + salt) % 10
+                si += 1
+                acc.append(a_stock(cx.k_stock(j + 1, w), q))
+                sum_q[lost] += q
+                n_q[lost] += 1
+            else:
+                assert j < 9 * cpd
+                h = int(hs[ci])
+                ci += 1
+                acc.append(a_pcust(cx.k_cust(j % cpd + 1, j // cpd + 1, w), h))
+                sum_h[lost] += h
+        b.txn(*acc)
+    assert pi == n_priv and k == L
+    e = b.epoch()
+    e.owner = owner_bytes(cx, e, world)
+    c = np.ones(len(slots), np.uint8)
+    c[lad] = np.arange(L) % 2 == 0
+    exp = {cc: c.copy() for cc in A.LOCKING + ("OCC",)}
+    exp["CALVIN"] = np.ones(len(slots), np.uint8)
+    # the rule's premises
+    txn = e.acc_txn()
+    is_link = (e.tables == T_CUST) & ((e.keys.astype(np.int64) - 1) // cpd % 10 == LINK_DIST % 10)
+    is_dist = e.tables == T_DIST
+    rest = ~(is_link | is_dist)
+    pairs = e.tables[rest].astype(np.int64) << 40 | e.keys[rest].astype(np.int64)
+    assert len(np.unique(pairs)) == int(rest.sum()), "a private row is used twice"
+    assert int(is_link.sum()) == 2 * L and (e.types == WR).all()
+    for kd in np.unique(e.keys[is_dist]):
+        writers = txn[is_dist & (e.keys == kd)]
+        assert len(np.unique(writers)) == len(writers) and int(c[writers].sum()) <= 1, "two committing NewOrders of a district"
+    if L >= 2:
+        lp = e.owner[is_link].reshape(L, 2)
+        assert (lp[:, 0] != lp[:, 1]).all(), "consecutive links on one partition"
+    info = dict(lad=np.array(lad, np.int64), nod=nod, dist=dist, sum_h=sum_h, sum_q=sum_q, n_q=n_q,
+                n_cust=ci, n_link=2 * L, lost_pay=sum(1 for t in np.flatnonzero(c == 0) for a in
+                                                   range(int(e.txn_begin[t]), int(e.txn_begin[t + 1]))
+                                                   if e.tables[a] == T_CUST))
+    return e, exp, info
+
+
+def ragged_tpcc(world, epochs_slots, own):
+    """A TCase of ragged_tpcc_epoch's epochs (salt: the epoch's number), run in
+    order on one database."""
+    cx = ctx_world(world)
+    built_ = [ragged_tpcc_epoch(world, slots, own, salt=k) for k, slots in enumerate(epochs_slots)]
+    epochs = [b[0] for b in built_]
+
+    def applied(cc, k):
+        return built_[k][1][cc]
+
+    def closed(cc, k, before, after, oid):
+        e, exp, info = built_[k]
+        all_ = cc == "CALVIN"
+        # payments: every applied one adds its amount to C_YTD_PAYMENT, takes it from C_BALANCE
+        want = info["sum_h"][False] + (info["sum_h"][True] if all_ else 0)
+        for col, sign in ((1, 1), (0, -1)):
+            d = after[T_CUST][col].view(np.float64) - before[T_CUST][col].view(np.float64)
+            assert (d == np.round(d)).all() and int(d.astype(np.int64).sum()) == sign * want
+        pays = info["n_cust"] + info["n_link"] - (0 if all_ else info["lost_pay"])
+        grown = after[T_CUST][2].view(np.float64) - before[T_CUST][2].view(np.float64)
+        assert int(np.round(grown).sum()) == pays
+        # stock: one write a row
+        sq = info["sum_q"][False] + (info["sum_q"][True] if all_ else 0)
+        nq = info["n_q"][False] + (info["n_q"][True] if all_ else 0)
+        assert int((after[T_STOCK][1].view(np.int64) - before[T_STOCK][1].view(np.int64)).sum()) == sq
+        assert int((after[T_STOCK][2] != before[T_STOCK][2]).sum()) == nq
+        assert int((after[T_STOCK][2].view(np.int64) - before[T_STOCK][2].view(np.int64)).sum()) == nq
+        # districts: the committing NewOrder takes D_NEXT_O_ID + 1; under CALVIN all of them, in sequence order
+        by_d = {}
+        for slot in sorted(info["nod"]):
+            by_d.setdefault(info["nod"][slot], []).append(slot)
+        c = exp[cc]
+        took = 0
+        for kd, txns in by_d.items():
+            r = int(cx.row(T_DIST, kd))
+            first = int(before[T_DIST][1][r])
+            ap = [t for t in txns if c[t]]
+            assert [int(oid[t]) for t in ap] == list(range(first + 1, first + 1 + len(ap)))
+            assert int(after[T_DIST][1][r]) == first + len(ap) and (all_ or len(ap) <= 1)
+            took += len(ap)
+        assert int((oid != 0).sum()) == took
+        assert all(np.array_equal(after[t][col], before[t][col]) for t in (T_WH, T_ITEM) for col in range(3))
+
+    return TCase(cx, epochs, applied, closed, extra=dict(world=world, own=own, info=[b[2] for b in built_]))
+
+
+# ---- the cuts of a TpccEpoch (adversarial.contiguous_chunks / strided_chunks
+# / trim_tail, carrying tables, args and owner)
+def _take(e, ids):
+    tb = e.txn_begin.astype(np.int64)
+    lens = np.diff(tb)[ids]
+    ltb = np.zeros(len(ids) + 1, np.int64)
+    ltb[1:] = np.cumsum(lens)
+    idx = np.repeat(tb[ids] - ltb[:-1], lens) + np.arange(int(ltb[-1]))
+    return T.TpccEpoch(e.keys[idx].copy(), e.types[idx].copy(), ltb.astype(np.uint32), e.tables[idx].copy(),
+                       e.args[idx].copy(), None, None if e.owner is None else e.owner[idx].copy())
+
+
+def contiguous_chunks(e, world):
+    tpr = (e.n_txn + world - 1) // world
+    return [_take(e, np.arange(min(r * tpr, e.n_txn), min((r + 1) * tpr, e.n_txn))) for r in range(world)], tpr
+
+
+def strided_chunks(e, world):
+    tpr = (e.n_txn + world - 1) // world
+    return [_take(e, np.arange(q, e.n_txn, world)) for q in range(world)], tpr
+
+
+def trim_tail(b):
+    n = np.flatnonzero(np.diff(b.txn_begin.astype(np.int64)))
+    return T.TpccEpoch(b.keys, b.types, b.txn_begin[:(int(n[-1]) + 2) if n.size else 1].copy(), b.tables, b.args,
+                       None, b.owner)
+
+
+def cut(e, world, order):
+    """the origins' batches of global epoch `e` (trailing empty txns dropped)
+    and txns_per_rank"""
+    parts, tpr = strided_chunks(e, world) if order == "position" else contiguous_chunks(e, world)
+    return [trim_tail(p) for p in parts], tpr
+
+
+def padded(e, n_txn):
+    """`e` with empty txns appended up to n_txn: the epoch the partitioned run
+    decides when the origins' slots outnumber the txns"""
+    tb = np.concatenate([e.txn_begin, np.full(n_txn - e.n_txn, e.txn_begin[-1], np.uint32)])
+    return T.TpccEpoch(e.keys, e.types, tb, e.tables, e.args, None, e.owner)
+
+
+# ---- family 8's shapes (per-origin slot lists through adversarial.arrange)
+PART_WORLDS = (2, 3)
+PART_SHAPES = ("edges", "mix")
+MIX_TPR = 37
+
+
+def _tsegment(total):
+    """one origin's batch of `total` accesses in ladder txns of 31; where it
+    spans more than a tile, a txn of 33 accesses sits across the first edge"""
+    X = A.structural_constants()["kOwnerTile"]
+    if total < X + MAX_TXN_ACC:
+        return A._fill(total, 31)
+    return A._fill(X - 16, 31) + [MAX_TXN_ACC - 2] + A._fill(total - X - 17, 31)
+
+
+def part_sizes():
+    X = A.structural_constants()["kOwnerTile"]
+    return [X - 1, X, X + 1, 2 * X + 1]
+
+
+SMALL_BATCH = [0, ONE, 3, EMPTY, 31, 1, EMPTY, ONE, 12]
+
+
+def part_slots(shape, world, order):
+    """(slot lists of the shape's epochs in sequence order, txns_per_rank)
+      edges  four epochs: one origin hands over kTile - 1, kTile, kTile + 1,
+             2 * kTile + 1 accesses in turn (the owner split's tile), the
+             origin before it nothing at all, a third a small batch
+      mix    two epochs of MIX_TPR txns an origin (neither a multiple of
+             world nor of 64) mixing 0-, 1-, 2-, ... 33-access txns"""
+    if shape == "edges":
+        per_epoch = []
+        for k, size in enumerate(part_sizes()):
+            per = [list(SMALL_BATCH) for _ in range(world)]
+            per[k % world] = []
+            per[(k + 1) % world] = _tsegment(size)
+            per_epoch.append(per)
+        tpr = max(len(s) for per in per_epoch for s in per)
+        return [A.arrange(per, order, tpr) for per in per_epoch], tpr
+    assert shape == "mix" and MIX_TPR % world and MIX_TPR % 64
+    pat = [EMPTY, 31, ONE, 0, EMPTY, 0, 31, 7, ONE, 12, 1]
+    return [[pat[(i + 3 * k) % len(pat)] for i in range(MIX_TPR * world)] for k in range(2)], MIX_TPR
+
+
+@functools.lru_cache(maxsize=None)
+def part_case(shape, world, own, order):
+    slots, tpr = part_slots(shape, world, order)
+    case = ragged_tpcc(world, slots, own)
+    case.extra.update(tpr=tpr, order=order, shape=shape)
+    return case

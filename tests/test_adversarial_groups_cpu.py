@@ -29,6 +29,14 @@ each edge; the kernels are not instrumented for it:
       kMaxPos-access txns, 63 empties beside one long txn, 64 long txns; an
       owner that receives nothing and one that receives everything, at world
       3 and 8
+  k_owner_* / k_ilist_bounds / k_ilist_move / k_il_begin / k_il_commits (the
+  per-epoch list protocol, dv_epoch_run_part in mode 1)
+      test_list_protocol_edges, test_list_protocol_wave_mix_equal_starts: home
+      batches of kOwnerTile - 1, kOwnerTile, kOwnerTile + 1 and
+      2 * kOwnerTile + 1 accesses and of none, owners that receive nothing or
+      everything, records in a home tile past the first, and position-major
+      segments that start, end and are interleaved with txns that have no
+      record at the owner (equal starts under the lower bound)
 """
 import functools
 
@@ -229,3 +237,113 @@ def test_wave_mix(world, own):
                 used = np.flatnonzero(m)
                 inner += bool(used.size and (m[:used[-1]] == 0).any())
             assert inner, "not dense: these batches go wide, or bring their boundaries"
+
+
+# ---- the list protocol (dv_epoch_run_part in mode 1), one epoch at a time:
+# what test_wave_mix_part and test_segment_edges_part put in front of the
+# owner split (k_owner_count / k_owner_scan / k_owner_scatter, tiles of
+# kOwnerTile home accesses) and of the position-major interleave
+# (k_ilist_bounds' lower bound per txn, k_ilist_move, k_il_begin, k_il_commits)
+KT = K["kOwnerTile"]
+
+
+def _owner_view(p, world, tpr):
+    """of one origin's batch, per owner (row % world): its record count, the
+    home tiles its records sit in, and which of the origin's tpr txn slots
+    have a record there"""
+    tb = p.txn_begin.astype(np.int64)
+    own = (p.keys % np.uint64(world)).astype(np.int64)
+    txn = np.repeat(np.arange(p.n_txn), np.diff(tb))
+    out = []
+    for o in range(world):
+        at = np.flatnonzero(own == o)
+        has = np.zeros(tpr, bool)
+        has[txn[at]] = True
+        out.append((len(at), set((at // KT).tolist()), has))
+    return out
+
+
+def _runs_without(has):
+    """lengths of the runs of txns without a record, in order"""
+    d = np.diff(np.r_[0, (~has).astype(np.int64), 0])
+    return (np.flatnonzero(d == -1) - np.flatnonzero(d == 1)).tolist()
+
+
+@functools.lru_cache(maxsize=None)
+def _segments_own(world, order, own):
+    return A.segment_edge_group(world, order, own)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("own", A.OWNERSHIPS)
+@pytest.mark.parametrize("world", [3, 4])
+def test_list_protocol_edges(world, own, order):
+    """test_segment_edges_part's epochs, cut as it cuts them.  The owner
+    split tiles the home batch by kOwnerTile == kXTile accesses, so family 9's
+    segment sizes are its edges: home batches of kTile - 1, kTile, kTile + 1
+    and 2 * kTile + 1 accesses (1, 1, 2 and 3 tiles) and one of 0 (no txns:
+    n_home == 0).  part0: one owner receives every record, the others none
+    (n_recv == 0); skip_last: the last owner receives none.  spread: every
+    owner has records in a home tile b > 0 of the batches of more than a tile
+    (counts[o][b], b > 0: its run of records in the send area crosses the tile
+    edge), and position-major every origin that hands over fewer txns than
+    txns_per_rank leaves every owner a segment whose last txns (130 of 263)
+    have no record: k_ilist_bounds' lower bounds end in equal starts up to the
+    segment's length."""
+    assert KT == X, "the owner split's tile is the landed tile: the segment sizes are its edges too"
+    cases, tpr = _segments_own(world, order, own)
+    sizes, later_tile, tail_runs = set(), np.zeros(world, np.int64), np.zeros(world, np.int64)
+    for case in cases:
+        parts, tpr_ = _round_trip(case, world, order)
+        assert tpr_ == tpr
+        recv = np.zeros(world, np.int64)
+        for p in parts:
+            sizes.add(p.n_acc)
+            assert (p.n_acc == 0) == (p.n_txn == 0)
+            for o, (n, tiles, has) in enumerate(_owner_view(p, world, tpr)):
+                recv[o] += n
+                later_tile[o] += bool(tiles - {0})
+                if n and order == "position" and p.n_txn < tpr:
+                    runs = _runs_without(has)
+                    assert not has[-1] and runs[-1] >= tpr - p.n_txn == 130
+                    tail_runs[o] += 1
+        assert sum(p.n_txn == 0 for p in parts) == 1
+        if own == "part0":
+            assert recv[0] == case.epoch.n_acc and not recv[1:].any()
+        elif own == "skip_last":
+            assert recv[-1] == 0 and recv[:-1].min() > 0
+        else:
+            assert recv.min() > 0
+    assert sizes == {0, KT - 1, KT, KT + 1, 2 * KT + 1}
+    used = world - 1 if own == "skip_last" else 1 if own == "part0" else world
+    assert (later_tile[:used] >= 1).all(), "an owner's records in a home tile past the first (the 2 * kTile + 1 batch)"
+    if order == "position":
+        assert (tail_runs[:used] >= world).all(), "segments that end in txns without a record"
+
+
+@pytest.mark.parametrize("world", [3, 8])
+def test_list_protocol_wave_mix_equal_starts(world):
+    """test_wave_mix_part's (1, position) run under `spread`: origin 0's first
+    slot is the epoch's first, an empty txn, so every owner's segment from
+    origin 0 starts with a txn without a record (tbo[0] == tbo[1] == 0); and
+    since most txns hold 0, 1 or 2 accesses, every owner's segment from every
+    origin has txns without a record inside it, in runs of up to 24 at world 3
+    (59, 58 and 70 of origin 0's 128 txns at owners 0, 1, 2) and of up to 12
+    at world 8 (31 of 48).  The batch crosses a home tile edge at world 3
+    (5,822 .. 6,076 accesses an origin) and stays inside one at world 8."""
+    e = _wave(world, "spread").epoch
+    parts, tpr = A.cut(e, world, "position")
+    for q, p in enumerate(parts):
+        for o, (n, tiles, has) in enumerate(_owner_view(p, world, tpr)):
+            runs = _runs_without(has)
+            assert n > 0 and sum(runs) >= tpr // 3 and max(runs) >= 4
+            assert has[-1], "the wave mix's last slots hold txns of kMaxPos accesses: a record at every owner"
+            if q == 0:
+                assert not has[0] and np.array_equal(has, has[:tpr])
+            assert (tiles == {0, 1}) == (world == 3)
+    v = _owner_view(parts[0], world, tpr)
+    if world == 3:
+        assert [int((~has).sum()) for _, _, has in v] == [59, 58, 70] and tpr == 128
+        assert max(max(_runs_without(has)) for _, _, has in v) == 24
+    else:
+        assert int((~v[0][2]).sum()) == 31 and tpr == 48

@@ -25,6 +25,11 @@ can take:
 origin-major (contiguous cut) and position-major (strided cut; not CALVIN,
 which keeps the sequencer's order).  One engine group serves all forms and
 orders of a test, the oracle's table running along.
+
+The per-epoch list protocol (dv_epoch_run_part in mode 1: the owner split,
+and position-major k_ilist_bounds / k_ilist_move / k_il_begin / k_il_commits)
+takes the wave mix and the segment edges one epoch at a time, in both orders
+(test_wave_mix_part, test_segment_edges_part).
 """
 import functools
 
@@ -52,7 +57,7 @@ def _gpu():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a visible MI355X")
     yield
-    for f in (_segments, _moves, _waves):
+    for f in (_segments, _moves, _waves, _segments_own):
         f.cache_clear()
 
 
@@ -286,13 +291,16 @@ def test_wave_mix_groups(cc, order, world, own):
 def test_wave_mix_part(cc, world, own):
     """The per-epoch protocols over the wave mix: the list protocol (mode 1:
     k_owner_count / scan / scatter see an owner that receives nothing and one
-    that receives everything), the replicated one (mode 2) and its
-    position-major form."""
+    that receives everything) in both orders -- position-major it interleaves
+    the received records itself, k_ilist_bounds / k_ilist_move, over segments
+    that start with txns without a record at the owner -- the replicated one
+    (mode 2) and its position-major form."""
     case = A.wave_mix(world, own)
     e = case.epoch
     tpr = e.n_txn // world
     rows_pp = -(-case.rows // world)
-    modes = [(1, "origin"), (2, "origin")] + ([] if cc == "CALVIN" else [(2, "position")])
+    # (with the position flag CALVIN keeps origin order, _orders)
+    modes = [(mode, order) for mode in (1, 2) for order in _orders(cc)]
     for mode, order in modes:
         parts, tpr_ = A.cut(e, world, order)
         assert tpr_ == tpr
@@ -324,6 +332,57 @@ def test_wave_mix_part(cc, world, own):
         finally:
             for eng in engines:
                 eng.close()
+
+
+# ---- segment edges through the list protocol: the owner split's tiles, k_ilist_bounds / k_ilist_move
+@functools.lru_cache(maxsize=None)
+def _segments_own(world, order, own):
+    return A.segment_edge_group(world, order, own)
+
+
+@pytest.mark.parametrize("cc,order", [(cc, order) for cc in A.CCS for order in _orders(cc)])
+@pytest.mark.parametrize("own", A.OWNERSHIPS)
+@pytest.mark.parametrize("world", [3, 4])
+def test_segment_edges_part(cc, order, world, own):
+    """The segment-edge epochs one at a time through the list protocol (mode
+    1), one dv_epoch_run_part call each on one engine group, the oracle's
+    table running along: home batches of kTile - 1, kTile, kTile + 1 and
+    2 * kTile + 1 accesses in front of k_owner_count / scan / scatter, an
+    origin without txns (n_home == 0), and with the rows all on partition 0 or
+    never on the last one owners that receive nothing (n_recv == 0).  Every
+    batch is handed over with its real n_txn: position-major the shorter
+    segments end in txns without a record (test_adversarial_groups_cpu.py,
+    test_list_protocol_edges)."""
+    cases, tpr = _segments_own(world, order, own)
+    rows_pp = -(-max(case.rows for case in cases) // world)
+    cap = max(case.epoch.n_acc for case in cases) + 4096  # (an owner may receive every record)
+    engines = _engines(cc, world, rows_pp, tpr, [cap] * world, 1 | (POSITION if order == "position" else 0),
+                       asynchronous=True)
+    table = _Table(rows_pp, world)
+    try:
+        for k, case in enumerate(cases):
+            what = f"epoch {k} {order}-major"
+            parts, tpr_ = A.cut(case.epoch, world, order)
+            assert tpr_ == tpr and min(p.n_txn for p in parts) == 0
+            c_ref, st_ref = table.run(cc, case)
+            exp = case.expected_commit(cc)
+            if order == "position":
+                exp, c_ref = _origin_order(exp, world, tpr), _origin_order(c_ref, world, tpr)
+            res = _run_group(engines, [DeviceEpoch(p) for p in parts], tpr)
+            digest = writes = 0
+            for r, x in enumerate(res):
+                assert not isinstance(x, Exception), f"{what}: rank {r}: {x}"
+                c, st = x
+                assert np.array_equal(c, exp), f"{what}: rank {r}: {int((c != exp).sum())} txns off the formula"
+                assert np.array_equal(c, c_ref)
+                assert st.committed == st_ref.committed == int(exp.sum())
+                digest = (digest + st.read_digest) % (1 << 64)
+                writes += st.write_cnt
+            assert digest == st_ref.read_digest and writes == st_ref.write_cnt, what
+            table.check_rows(engines, what)
+    finally:
+        for eng in engines:
+            eng.close()
 
 
 # ---- the group's capacity refusal (run_group: in > r[4])
