@@ -3650,6 +3650,33 @@ int dv_round_log(dv_ctx *c, uint32_t *live, uint32_t *undecided, uint32_t cap) {
     return (int)n;
 }
 
+// the epoch's own sort call (sort_rows: pairs, counts, digit_tot, the context's
+// DV_FLAG_LSD_SORT) on the caller's keys; no other state of the context changes
+int dv_sort_rows_device(dv_ctx *c, const uint64_t *d_keys, uint64_t n, const uint32_t *d_n, int key_bits,
+                        uint64_t *d_out, uint32_t *launches) {
+    KProfScope kps_(c);
+    if (!c || !d_keys || !d_out || !launches) return DV_ERR_ARG;
+    if (n > c->cfg.max_acc || key_bits < 1 || key_bits > 32) return DV_ERR_ARG;
+    if (c->phase != 0) return DV_ERR_STATE;
+    *launches = 0;
+    if (n == 0) return DV_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipMemcpyAsync(c->pairs[0], d_keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    const int res = sort_rows(c, n, key_bits, nullptr, false, d_n);
+    HIPCHK(hipGetLastError());
+    uint64_t m = n;
+    if (d_n) {
+        uint32_t cnt = 0;
+        HIPCHK(hipMemcpyAsync(&cnt, d_n, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (cnt < m) m = cnt;
+    }
+    if (m) HIPCHK(hipMemcpyAsync(d_out, c->pairs[res], m * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *launches = sort_launches(c, n, key_bits, false, d_n != nullptr);
+    return DV_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -233,6 +233,8 @@ SIGNATURES = [
     ("dv_epoch_round_wait", ctypes.c_int, [_vp, ctypes.c_uint32, _P(ctypes.c_uint32)]),
     ("dv_epoch_finish", ctypes.c_int, [_vp, _vp, _P(Stats)]),
     ("dv_round_log", ctypes.c_int, [_vp, _P(ctypes.c_uint32), _P(ctypes.c_uint32), ctypes.c_uint32]),
+    ("dv_sort_rows_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_int, _vp,
+                                           _P(ctypes.c_uint32)]),
     ("dv_epoch_errors_local", ctypes.c_int, [_vp, _vp]),
     ("dv_epoch_errors_combined", ctypes.c_int, [_vp, _vp]),
     ("dv_set_async_limits", ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32]),

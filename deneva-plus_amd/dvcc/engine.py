@@ -1028,6 +1028,23 @@ class CCEngine:
         n = L.lib().dv_round_log(self._ctx, live, und, 64)
         return list(live[:n]), list(und[:n])
 
+    def sort_rows(self, d_keys, key_bits, d_n=None, d_out=None):
+        """The epoch's row-queue sort on the caller's keys (dv_sort_rows_device):
+        d_keys is a device tensor of row << 32 | payload words (int64 or
+        uint64 storage), d_n an optional one-element device count (int32
+        storage) with len(d_keys) its bound.  Returns (d_out, launches): the
+        first min(len(d_keys), d_n) words of d_out (a fresh tensor unless
+        given) hold the sorted keys; launches tells the path (2: the bucket
+        sort, else the LSD passes).  Diagnostic."""
+        import torch
+        if d_out is None:
+            d_out = torch.empty_like(d_keys)
+        launches = ctypes.c_uint32(0)
+        self._after_torch()
+        L.check(L.lib().dv_sort_rows_device(self._ctx, _ptr(d_keys), int(d_keys.numel()), _ptr(d_n), int(key_bits),
+                                            _ptr(d_out), ctypes.byref(launches)), "dv_sort_rows_device")
+        return d_out, int(launches.value)
+
     # ---- staged form (multi-partition epochs)
     def begin(self, dep, d_grant=None):
         self._after_torch()

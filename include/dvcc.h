@@ -815,6 +815,21 @@ int dv_set_prefix(dv_ctx *ctx, uint32_t prefix_txns);
  * number of rounds logged (at most cap, and at most 64) */
 int dv_round_log(dv_ctx *ctx, uint32_t *live, uint32_t *undecided, uint32_t cap);
 
+/* diagnostics: the row-queue sort of an epoch on the caller's keys (device
+ * memory; a key is row << 32 | payload, row < 2^key_bits).  d_keys[0, n) is
+ * sorted stably by row exactly as an epoch sorts its accesses -- the context's
+ * own buffers and DV_FLAG_LSD_SORT, the count either n or, with d_n, the
+ * smaller of n and *d_n (a count on the device, n its bound) -- and the first
+ * min(n, *d_n) keys of the result are copied to d_out.  The order among rows is
+ * ascending by row for the LSD passes and by the row's hash for the bucket
+ * sort; rows are grouped and each row's keys keep their input order either
+ * way.  *launches: the sort's timed launches (dv_stats.sort_passes), which
+ * tell the path.  DV_ERR_ARG: a null pointer, n above the context's max_acc,
+ * key_bits outside 1..32; n == 0 launches nothing.  Synchronises the stream.
+ * Between epochs; no table is needed. */
+int dv_sort_rows_device(dv_ctx *ctx, const uint64_t *d_keys, uint64_t n, const uint32_t *d_n, int key_bits,
+                        uint64_t *d_out, uint32_t *launches);
+
 /* host-side epoch builder */
 int dv_ycsb_gen(const dv_ycsb_params *p, uint64_t seed, uint32_t home_part, uint32_t n_txn,
                 uint64_t *keys, uint8_t *types, uint32_t *txn_begin);

@@ -23,7 +23,7 @@ def test_header_declares_expected_surface():
     syms = _declared_symbols()
     for s in ["dv_open", "dv_close", "dv_epoch_run", "dv_epoch_run_device", "dv_load_table",
               "dv_read_rows", "dv_epoch_begin", "dv_epoch_round_local", "dv_epoch_round_apply",
-              "dv_epoch_finish", "dv_ycsb_gen"]:
+              "dv_epoch_finish", "dv_ycsb_gen", "dv_sort_rows_device"]:
         assert s in syms
 
 

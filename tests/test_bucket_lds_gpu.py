@@ -114,12 +114,17 @@ def _hot_row_epoch(rows, n_txn, seed, R=4):
     return Epoch(keys.reshape(-1), types.reshape(-1), (np.arange(n_txn + 1) * R).astype(np.uint32))
 
 
-@pytest.mark.parametrize("log_rows", [16, 22, 26])
+@pytest.mark.parametrize("log_rows", [16, 22, 26, "26+1", "27+1"])
 def test_pass_counts(log_rows):
     """8, 14 and 18 row bits above the bucket digit: one, two and three passes
     over the single tag array (and over global memory for the hot row's
-    20,000-key bucket), whole epochs and prefix-kill stages"""
-    rows = 1 << log_rows
+    20,000-key bucket), whole epochs and prefix-kill stages.  "26+1", "27+1":
+    2^26 + 1 and 2^27 + 1 rows, which the runtime gives 27 and 28 key bits --
+    512 and 1,024 buckets behind a hashed 9- and 10-bit first pass"""
+    extra = 0
+    if isinstance(log_rows, str):
+        log_rows, extra = (int(x) for x in log_rows.split("+"))
+    rows = (1 << log_rows) + extra
     g = YCSBQueryGenerator(rows, zipf_theta=0.9)
     eps = [g.gen(30_000, 151 + log_rows), _hot_row_epoch(rows, 20_000, 152 + log_rows)]
     tab = O.YcsbTable(rows)
