@@ -739,14 +739,19 @@ __global__ __launch_bounds__(kBlock) void k_bo_gather_count(const uint32_t *__re
 
 // every txn's boundary, then the block streams its txns' accesses from the
 // pool: an access's txn by a binary search over the block's output starts in
-// LDS (non-decreasing: an exclusive scan), as k_carry_copy
+// LDS (non-decreasing: an exclusive scan), as k_carry_copy.  ARGS (the TPC-C
+// loop): an access's operation word comes with it, as in k_carry_copy and
+// k_refill_fresh -- one more 8-byte gather from the same contiguous run of the
+// txn, one more coalesced store
+template <bool ARGS>
 __global__ __launch_bounds__(kBlock) void k_bo_gather_copy(
     const uint32_t *__restrict__ tot, uint32_t n_out, const uint64_t *__restrict__ oids,
     const uint64_t *__restrict__ pkeys, const uint8_t *__restrict__ ptypes, const uint8_t *__restrict__ ptables,
     const uint32_t *__restrict__ ptb, uint32_t pool_n, const uint32_t *__restrict__ precs,
     uint64_t *__restrict__ okeys, uint8_t *__restrict__ otypes, uint32_t *__restrict__ otxn,
     uint8_t *__restrict__ otables, uint32_t *__restrict__ orecs, uint32_t *__restrict__ otb,
-    uint32_t *__restrict__ n_acc_dev, uint64_t acc_cap, RefillBackoff bo) {
+    uint32_t *__restrict__ n_acc_dev, uint64_t acc_cap, RefillBackoff bo, const uint64_t *__restrict__ pargs,
+    uint64_t *__restrict__ oargs) {
     __shared__ uint32_t lds4[4];
     __shared__ uint32_t s_st[kCarryTpb], s_p0[kCarryTpb];
     if (tot[4]) return;
@@ -782,6 +787,7 @@ __global__ __launch_bounds__(kBlock) void k_bo_gather_copy(
         otypes[o] = ptypes[a];
         otxn[o] = blockIdx.x * kCarryTpb + q;
         if (otables) otables[o] = ptables ? ptables[a] : 0;
+        if (ARGS) oargs[o] = pargs[a];
     }
 }
 
@@ -820,8 +826,15 @@ static void launch_refill_backoff(hipStream_t s, const RefillReq &q) {
     DV_LAUNCH(k_bo_spill, gs < 1 ? 1 : (gs > 1024 ? 1024 : gs), kBlock, 0, s, tot, bo);
     DV_LAUNCH(k_bo_gather_count, nbo, kBlock, 0, s, tot, n_out, q.pool.tb, pool_n, trk.oids, trk.k_next, bo);
     DV_LAUNCH(k_bo_scan, 1, kBlock, 0, s, bo.gb, nbo, bo.bw + BW_GTOT);
-    DV_LAUNCH(k_bo_gather_copy, nbo, kBlock, 0, s, tot, n_out, trk.oids, p.keys, p.types, p.tables, q.pool.tb, pool_n,
-              p.recs, o.keys, o.types, o.txn, o.tables, o.recs, o.tb, o.n_acc_dev, q.acc_bound, bo);
+    const uint64_t *no_args = nullptr;
+    if (o.args)
+        DV_LAUNCH((k_bo_gather_copy<true>), nbo, kBlock, 0, s, tot, n_out, trk.oids, p.keys, p.types, p.tables,
+                  q.pool.tb, pool_n, p.recs, o.keys, o.types, o.txn, o.tables, o.recs, o.tb, o.n_acc_dev, q.acc_bound,
+                  bo, p.args, o.args);
+    else
+        DV_LAUNCH((k_bo_gather_copy<false>), nbo, kBlock, 0, s, tot, n_out, trk.oids, p.keys, p.types, p.tables,
+                  q.pool.tb, pool_n, p.recs, o.keys, o.types, o.txn, o.tables, o.recs, o.tb, o.n_acc_dev, q.acc_bound,
+                  bo, no_args, o.args);
     if (nb) {
         const uint32_t gf = (trk.n_bins + 4 + kBlock - 1) / kBlock;
         DV_LAUNCH(k_bo_fold, gf, kBlock, 0, s, tot, trk, bo);

@@ -168,9 +168,11 @@ struct dv_ctx {
     // (RefillBackoff); lost_seen: that count as the last loop call read it.
     // Under decision lanes the ring, the wait partials and the lost count are
     // lanes[0]'s, and every lane brings its own plan words and block counts
-    // (backoff_at).
+    // (backoff_at).  tpcc: attached through dv_tpcc_closed_loop_backoff, for
+    // the TPC-C loop, which takes no other attachment.
     struct LoopBo {
         bool on = false;
+        bool tpcc = false;
         uint32_t lanes = 1;
         dv_loop_backoff t{};
         uint8_t *aborts[2 * kMaxLanes] = {};
@@ -3364,20 +3366,23 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
     KProfScope kps_(c);
     if (!c || !pool_args || !buf_args || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
-    if (c->cfg.cc_alg == DV_CALVIN || c->comm || c->bo.on) return DV_ERR_STATE;  // (bo: the YCSB loops only)
+    if (c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
+    if (c->bo.on && !c->bo.tpcc) return DV_ERR_STATE;  // (a ring attached for the YCSB loops)
     uint64_t bound = 0;
     int r = loop_check(c, pool, pool_begin, cursor, n_txn, bufs, 2, buf_cap, n_epochs, true, &bound);
     if (!r && (!buf_args[0] || !buf_args[1])) r = DV_ERR_ARG;
     if (r) return r;
     HIPCHK(hipSetDevice(c->cfg.device));
     r = carry_bufs(c, carry_blocks(n_txn));
+    if (!r) r = backoff_bufs(c, carry_blocks(n_txn), c->bo.on);
     if (r) return r;
     const LoopForm form{};
     const RefillReq req = loop_refill(pool, pool_args, pool_begin, cursor, n_txn, bound, form);
     RefillTrack tw;
+    RefillBackoff bw;
     if (!resume)
-        r = enqueue_refill(c, req, form, nullptr, bufs[0], track_at(c, false, 0, 0, 1, 0, 1, &tw), nullptr, nullptr,
-                           buf_args[0]);
+        r = enqueue_refill(c, req, form, nullptr, bufs[0], track_at(c, false, 0, 0, 1, 0, 1, &tw),
+                           backoff_at(c, c, 0, 0, &bw), nullptr, buf_args[0]);
     for (uint32_t k = 0; !r && k < n_epochs; k++) {
         const uint32_t ib = k & 1, ob = (k + 1) & 1;
         const dv_epoch_dev d = loop_desc(bufs[ib], form, pool, n_txn, bound);
@@ -3385,7 +3390,7 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
                                      d_oids ? d_oids[k] : nullptr, sts ? &sts[k] : nullptr);
         if (!r)
             r = enqueue_refill(c, req, form, &bufs[ib], bufs[ob], track_at(c, true, k, k + 1, ib, ob, 1, &tw),
-                               nullptr, buf_args[ib], buf_args[ob]);
+                               backoff_at(c, c, ib, ob, &bw), buf_args[ib], buf_args[ob]);
     }
     if (r) {
         (void)hipStreamSynchronize(c->stream);
@@ -3393,7 +3398,7 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
     }
     HIPCHK(hipStreamSynchronize(c->stream));  // (the next epoch's refill: the caller may read it)
     c->trk.next += c->trk.on ? n_epochs : 0u;
-    return DV_OK;
+    return backoff_lost(c);
 }
 
 // The closed loop over decision lanes: epoch k on lanes[k % L]; each lane
@@ -3523,6 +3528,7 @@ int dv_closed_loop_backoff_lanes(dv_ctx *c, const dv_loop_backoff *bo, uint32_t 
         return DV_ERR_STATE;
     c->bo.on = true;
     c->bo.lanes = n_lanes;
+    c->bo.tpcc = false;
     c->bo.t = *bo;
     for (uint32_t b = 0; b < 2 * kMaxLanes; b++) c->bo.aborts[b] = b < 2 * n_lanes ? bo->aborts[b] : nullptr;
     c->bo.t.aborts = nullptr;  // (the caller's array is not kept)
@@ -3530,6 +3536,15 @@ int dv_closed_loop_backoff_lanes(dv_ctx *c, const dv_loop_backoff *bo, uint32_t 
 }
 
 int dv_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) { return dv_closed_loop_backoff_lanes(c, bo, 1); }
+
+// the same ring for dv_tpcc_epoch_run_closed_loop: the attachment says which
+// loop it is for
+int dv_tpcc_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) {
+    if (!c || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
+    const int r = dv_closed_loop_backoff_lanes(c, bo, 1);
+    if (!r) c->bo.tpcc = bo != nullptr;
+    return r;
+}
 
 }  // extern "C"
 

@@ -21,6 +21,6 @@ except Exception:  # pragma: no cover
 from ._lib import (CALVIN, CC_NAMES, HASH_MOD, HASH_YCSB, NO_WAIT, OCC, RD, SCAN, WAIT_DIE, WR,  # noqa
                    DvccError, lib)
 from .engine import CCEngine, ClosedLoopBufs, DeviceEpoch, Epoch, LoopBackoff, LoopTrack, comm_unique_id  # noqa: F401
-from .tpcc import TpccEngine, TpccLoopBufs  # noqa: F401
+from .tpcc import TpccEngine, TpccLoopBackoff, TpccLoopBufs  # noqa: F401
 from .ycsb import YCSBQueryGenerator, epoch_seed, sequence, sequence_position  # noqa: F401
 from .wire import CalvinDeviceWireIngress, DeviceWireIngress, TpccDeviceWireIngress, WireIngress  # noqa: F401,E402

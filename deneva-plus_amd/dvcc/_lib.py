@@ -309,6 +309,7 @@ SIGNATURES = [
     ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
     ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
     ("dv_closed_loop_backoff_lanes", ctypes.c_int, [_vp, _P(LoopBackoffDesc), ctypes.c_uint32]),
+    ("dv_tpcc_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
 ]
 
 _lib = None

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .engine import CCEngine, ClosedLoopBufs, DeviceEpoch, Epoch, _commit_ptrs, _ptr
+from .engine import CCEngine, ClosedLoopBufs, DeviceEpoch, Epoch, LoopBackoff, _commit_ptrs, _ptr
 
 TABLES = {"WAREHOUSE": L.T_WAREHOUSE, "DISTRICT": L.T_DISTRICT, "CUSTOMER": L.T_CUSTOMER,
           "ITEM": L.T_ITEM, "STOCK": L.T_STOCK, "CUST_LAST": L.T_CUST_LAST}
@@ -82,6 +82,33 @@ class TpccLoopBufs(ClosedLoopBufs):
         """buffer b's epoch as (DeviceEpoch, args) (reads its access count)"""
         dep = super().epoch(b, n_txn, max_txn_acc)
         return dep, self.args[b][:dep.n_acc]
+
+
+class TpccLoopBackoff(LoopBackoff):
+    """Exponential back-off for the TPC-C closed loop
+    (dv_tpcc_closed_loop_backoff): LoopBackoff over a LoopTrack of two
+    buffers, attached to a TpccEngine through the entry its loop accepts.  A
+    released txn's accesses come from the pool again with their table bytes
+    and operation words.  swap() goes with TpccLoopBufs.swap and
+    LoopTrack.swap after a call of n_epochs odd."""
+
+    def __init__(self, track, n_slots, slot_cap=None, device="cuda"):
+        if track.n_bufs != 2:
+            raise ValueError("TpccLoopBackoff: a tracker of two buffers")
+        super().__init__(track, n_slots, slot_cap, device)
+
+    def _attach(self):
+        arr = (ctypes.c_void_p * 2)(*[int(t.data_ptr()) for t in self.aborts])
+        d = L.LoopBackoffDesc(self.n_slots, self.slot_cap, self.park_ids.data_ptr(), self.park_aborts.data_ptr(),
+                              self.slot_count.data_ptr(), arr, self.ctr.data_ptr())
+        L.check(L.lib().dv_tpcc_closed_loop_backoff(self.engine._ctx, ctypes.byref(d)),
+                "dv_tpcc_closed_loop_backoff")
+
+    def detach(self):
+        if self.engine is not None:
+            L.check(L.lib().dv_tpcc_closed_loop_backoff(self.engine._ctx, None), "dv_tpcc_closed_loop_backoff")
+            self.engine._backoff = None
+            self.engine = None
 
 
 class TpccEngine(CCEngine):
@@ -178,9 +205,12 @@ class TpccEngine(CCEngine):
         pool_begin: its n_txn + 1 access offsets, int32 device tensor) from the
         device word `cursor` (int32 tensor, advanced).  bufs: TpccLoopBufs
         (allocated when None); d_commits / d_oids: a device tensor per epoch,
-        one for all, or None.  track: a LoopTrack attached to this engine.
+        one for all, or None.  track: a LoopTrack attached to this engine.  A
+        TpccLoopBackoff attached to this engine (after its tracker) backs the
+        retries off; it needs no argument here.
         Returns (stats list, bufs, cursor); the next epoch is in
-        bufs.epoch(n_epochs & 1)."""
+        bufs.epoch(n_epochs & 1): after an odd call TpccLoopBufs.swap,
+        LoopTrack.swap and TpccLoopBackoff.swap go together, in that order."""
         track = self._tracked(track, n_txn, 2)
         cursor, sts = self._loop_state(pool, cursor, n_epochs)
         if bufs is None:

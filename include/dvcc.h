@@ -637,7 +637,8 @@ int dv_closed_loop_track(dv_ctx *ctx, const dv_loop_track *trk);
  * one with a communicator (DV_ERR_STATE).  With a back-off attached through
  * this entry dv_epoch_run_closed_loop_lanes (n_lanes > 1) and
  * dv_tpcc_epoch_run_closed_loop return DV_ERR_STATE before any launch (the
- * lanes loop takes one attached through dv_closed_loop_backoff_lanes, below).
+ * lanes loop takes one attached through dv_closed_loop_backoff_lanes, below,
+ * the TPC-C loop one attached through dv_tpcc_closed_loop_backoff).
  * The refill is then a different chain (k_bo_count, k_bo_scan, k_bo_plan,
  * k_bo_park, k_bo_spill, k_bo_gather_count, k_bo_scan, k_bo_gather_copy,
  * k_bo_fold: dvcc_carry.hip), a no-op behind a halted or failed epoch like the
@@ -949,11 +950,41 @@ int dv_tpcc_epoch_carry(dv_ctx *ctx, const dv_epoch_dev *ep, const uint64_t *d_a
  * k + 1 is queued); a halted epoch is decided again synchronously before its
  * successor is rebuilt.  The epochs are exactly those of a host loop of
  * dv_tpcc_epoch_run_device + dv_tpcc_epoch_carry + the fresh txns
- * (tests/test_tpcc_closed_loop.py). */
+ * (tests/test_tpcc_closed_loop.py).  A tracker (dv_closed_loop_track,
+ * n_bufs == 2) is taken as the YCSB loop takes it; a back-off only when it was
+ * attached through dv_tpcc_closed_loop_backoff (below) -- one attached through
+ * dv_closed_loop_backoff or dv_closed_loop_backoff_lanes is DV_ERR_STATE
+ * before any launch, with cursor, tracker, ring and counters untouched.  With
+ * a back-off the call returns DV_ERR_ARG after its last epoch when ring
+ * entries were lost (capacity exceeded), as dv_epoch_run_closed_loop does. */
 int dv_tpcc_epoch_run_closed_loop(dv_ctx *ctx, const dv_epoch_dev *pool, const uint64_t *pool_args,
                                   const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_txn, dv_epoch_dev *bufs,
                                   uint64_t *const *buf_args, uint64_t buf_cap, uint32_t n_epochs, int resume,
                                   uint8_t *const *d_commits, uint64_t *const *d_oids, dv_stats *sts);
+
+/* Exponential back-off for the TPC-C closed loop
+ * (dv_tpcc_epoch_run_closed_loop), on top of its tracker.  The struct and the
+ * rule are dv_closed_loop_backoff's, word for word: the park after epoch k,
+ * the release of slot (k + 1) % D, the spill, the fresh txns from the cursor,
+ * the capacity bound n_txn * (D + log2 D), lost entries (counted, not written,
+ * DV_ERR_ARG after the call's last epoch), the histogram by abort count and
+ * counters[4].  One addition: a released txn's accesses are read from the pool
+ * again by its src with their table bytes and operation words (pool->tables,
+ * pool_args) -- the query is unchanged, a Payment by last name is looked up
+ * again.  D = 1 is the plain TPC-C loop bit for bit: epochs (operation words
+ * included), commit bytes, o_ids, tables, cursor, log, histogram, totals.
+ * The attachment says which loop it is for, as a lanes attachment says its
+ * lane count: the TPC-C loop takes a back-off attached through this entry and
+ * no other.  Requires a tracker with n_bufs == 2 attached to the context;
+ * detaching the tracker detaches the back-off; NULL detaches.  Refused at
+ * attach time: what dv_closed_loop_backoff refuses, with the same codes, and a
+ * context that is not DV_TPCC (DV_ERR_ARG).
+ * The refill chain is dv_closed_loop_backoff's, with the operation words in
+ * k_bo_gather_copy, queued behind each epoch's execution.  A halted decision
+ * is finished synchronously before its refill is queued, so every epoch is
+ * parked and built exactly once.  Without a back-off the loop launches exactly
+ * what it launched before. */
+int dv_tpcc_closed_loop_backoff(dv_ctx *ctx, const dv_loop_backoff *bo);   /* NULL detaches */
 
 /* TPC-C epochs over decision lanes (dv_open_lane on a DV_TPCC context), as
  * dv_epoch_run_device_lanes: epoch k decided on lanes[k % n_lanes], executions

@@ -18,7 +18,14 @@ lanes (dv_epoch_run_closed_loop_lanes under dv_closed_loop_backoff_lanes: one
 ring shared by the lanes, a txn's a-th abort costing L - 1 + min(2^(a-1), D)
 epochs) against the tracked plain lanes loop, whose every retry comes L
 epochs later; `--warmup` and `--epochs` are rounded up to multiples of 2 L
-(a resumed call continues each lane in its first buffer)."""
+(a resumed call continues each lane in its first buffer).
+
+`--tpcc` measures the same legs on the TPC-C closed loop
+(dv_tpcc_epoch_run_closed_loop under dv_tpcc_closed_loop_backoff,
+dvcc.TpccLoopBackoff) with bench.py's config-E parameters: `--tpcc-wh`
+warehouses (32), `--cc` (WAIT_DIE), 65,536 txns per epoch unless `--n-txn`
+says otherwise, a pool of two epochs' txns.  One context: TPC-C has no loop
+over decision lanes."""
 import argparse
 import json
 import os
@@ -35,36 +42,58 @@ import dvcc  # noqa: E402
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", type=int, default=16_777_216)
-    ap.add_argument("--n-txn", type=int, default=1_048_576)
+    ap.add_argument("--n-txn", type=int, default=None, help="txns per epoch (1,048,576; --tpcc: 65,536)")
     ap.add_argument("--slots", type=int, nargs="*", default=[2, 4, 8])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=40)
     ap.add_argument("--lanes", type=int, default=1)
+    ap.add_argument("--tpcc", action="store_true", help="the TPC-C closed loop at config E")
+    ap.add_argument("--tpcc-wh", type=int, default=32)
+    ap.add_argument("--cc", default="WAIT_DIE", help="--tpcc: NO_WAIT, WAIT_DIE or OCC")
     ap.add_argument("--out")
     a = ap.parse_args()
-    n_txn, nl = a.n_txn, max(1, a.lanes)
+    nl = max(1, a.lanes)
+    n_txn = a.n_txn if a.n_txn else (65_536 if a.tpcc else 1_048_576)
+    if a.tpcc and nl > 1:
+        ap.error("--tpcc: one context (TPC-C has no closed loop over decision lanes)")
     if nl > 1:
         a.warmup, a.epochs = (-(-v // (2 * nl)) * 2 * nl for v in (a.warmup, a.epochs))
-    gen = dvcc.YCSBQueryGenerator(a.rows, part_cnt=1, req_per_query=10, zipf_theta=0.9, txn_write_perc=1.0,
-                                  tup_write_perc=0.5, part_per_txn=1, strict_ppt=1, mpr=-1.0)
-    pool = gen.gen(2 * n_txn, dvcc.epoch_seed(0, 999))
-    dpool = dvcc.DeviceEpoch(pool)
-    pb = torch.from_numpy(pool.txn_begin.astype("int32")).cuda()
-    torch.cuda.set_stream(torch.cuda.Stream())
-    eng = dvcc.CCEngine("NO_WAIT", n_txn, n_txn * 10)
-    eng.set_stream(torch.cuda.current_stream().cuda_stream)
-    eng.load_ycsb_partition(a.rows)
+    if a.tpcc:  # (both set-ups: the pool uploaded before the engine's stream is made current)
+        from dvcc import tpcc as T
+        tp = T.tpcc_params(a.tpcc_wh)
+        pool = T.gen(tp, 2 * n_txn, dvcc.epoch_seed(0, 999))
+        dpool, pargs = T.device_epoch(pool)
+        pb = torch.from_numpy(pool.txn_begin.astype("int32")).cuda()
+        torch.cuda.set_stream(torch.cuda.Stream())
+        eng = T.TpccEngine(a.cc, tp, n_txn, seed=1)
+        eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        ring, what = T.TpccLoopBackoff, {"warehouses": a.tpcc_wh, "cc": a.cc, "pool_txns": pool.n_txn,
+                                         "max_txn_acc": int(dpool.max_txn_acc)}
+    else:
+        gen = dvcc.YCSBQueryGenerator(a.rows, part_cnt=1, req_per_query=10, zipf_theta=0.9, txn_write_perc=1.0,
+                                      tup_write_perc=0.5, part_per_txn=1, strict_ppt=1, mpr=-1.0)
+        pool = gen.gen(2 * n_txn, dvcc.epoch_seed(0, 999))
+        dpool = dvcc.DeviceEpoch(pool)
+        pb = torch.from_numpy(pool.txn_begin.astype("int32")).cuda()
+        torch.cuda.set_stream(torch.cuda.Stream())
+        eng = dvcc.CCEngine("NO_WAIT", n_txn, n_txn * 10)
+        eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        eng.load_ycsb_partition(a.rows)
+        ring, what = dvcc.LoopBackoff, {"rows": a.rows}
     lanes = [eng.open_lane() for _ in range(nl - 1)]
     total = a.warmup + a.epochs
     trk = dvcc.LoopTrack(n_txn, 2 * nl, log_cap=n_txn * total, epoch_cap=total, n_bins=64)
-    rings = {D: dvcc.LoopBackoff(trk, D) for D in a.slots}
+    rings = {D: ring(trk, D) for D in a.slots}
     # (the lanes decide epochs side by side: a commit array per epoch in flight)
     d_commit = torch.zeros(n_txn, dtype=torch.uint8, device="cuda") if nl == 1 else \
         [torch.zeros(n_txn, dtype=torch.uint8, device="cuda") for _ in range(2 * nl)]
     bufs = None
 
     def loop(n, cursor, resume):
+        if a.tpcc:
+            return eng.closed_loop(dpool, pargs, pb, n_txn, n, cursor=cursor, bufs=bufs, d_commits=d_commit,
+                                   resume=resume, track=trk)
         if nl == 1:
             return eng.closed_loop(dpool, pb, n_txn, n, cursor=cursor, bufs=bufs, d_commits=d_commit, resume=resume,
                                    track=trk)
@@ -124,7 +153,7 @@ def main():
 
     legs = [None] + list(a.slots)
     name = lambda D: "plain" if D is None else f"D{D}"  # noqa: E731
-    out = {"rows": a.rows, "n_txn": n_txn, "decision_lanes": nl, "warmup": a.warmup, "epochs": a.epochs, "rounds": a.rounds,
+    out = {**what, "n_txn": n_txn, "decision_lanes": nl, "warmup": a.warmup, "epochs": a.epochs, "rounds": a.rounds,
            "source": dvcc._lib.source_hash(), "legs": {name(D): [] for D in legs}}
     for _ in range(a.rounds):
         for D in legs:
