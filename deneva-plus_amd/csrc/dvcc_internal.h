@@ -749,6 +749,14 @@ uint32_t reply_tiles(uint32_t n_txn);
 void launch_reply_fields(hipStream_t s, const uint8_t *commit, uint32_t n_txn, const uint64_t *txn_id,
                          const uint64_t *cst, const uint32_t *rnode, uint64_t *o_txn_id, uint64_t *o_cst,
                          uint32_t *o_rnode, uint32_t *bc);
+// the reply mbufs packed on the device (dv_wire_respond_device), over
+// reply_tiles(in.n) tiles: the plan counts, scans and decides the call into
+// ws.res and writes the closing batch_off; the emit writes nothing unless the
+// plan's status is DV_OK
+void launch_rsp_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
+                     const ReplyWs &ws);
+void launch_rsp_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
+                     const ReplyWs &ws);
 
 // ---- prefix-kill epochs (dvcc_prefix.hip)
 // the row-state bitmap (2 bits per row): its 32-bit words for `rows` rows;

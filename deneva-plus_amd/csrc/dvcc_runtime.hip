@@ -4133,6 +4133,31 @@ int dv_wire_reply_fields_device(dv_ctx *c, const uint8_t *commit, uint32_t n_txn
     return DV_OK;
 }
 
+int dv_wire_respond_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wire_rsp_in *in, const dv_wire_rsp_out *out,
+                           dv_wire_rsp_result *res) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !in || !out || !res) return DV_ERR_ARG;
+    if (!out->out || !out->batch_off || !in->txn_id || !in->return_node) return DV_ERR_ARG;
+    if (!cfg->calvin && !in->client_startts) return DV_ERR_ARG;
+    if (in->commit && in->src) return DV_ERR_ARG;
+    if (!in->n_dest || in->n_dest > DV_WIRE_DEST_MAX || !cfg->node_cnt) return DV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;  // (written in whole dwords)
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // the compaction's scratch: the two are queued on the one stream, never at once
+    ReplyWs ws;
+    const uint32_t nt = reply_tiles(in->n);
+    int r = scratch_reserve(c, &c->reply_bc, &c->reply_bc_cap, reply_ws_layout(nullptr, nt, in->n_dest, ws));
+    if (!r) r = wire_host_ready(c);
+    if (r) return r;
+    reply_ws_layout(c->reply_bc, nt, in->n_dest, ws);
+    launch_rsp_plan(c->stream, *cfg, *in, *out, ws);
+    r = wire_record_then_emit(c, ws.res, sizeof(*res), [&] { launch_rsp_emit(c->stream, *cfg, *in, *out, ws); });
+    if (r) return r;
+    std::memcpy(res, c->wire_h, sizeof(*res));
+    return res->status;
+}
+
 int dv_epoch_reads_tb_only(const dv_ctx *c, uint32_t n_txn) {
     if (!c) return DV_ERR_ARG;
     static const uint32_t word = 0;  // (tb_epoch looks at which arrays are given, never through them)

@@ -1262,4 +1262,225 @@ void launch_reply_fields(hipStream_t s, const uint8_t *commit, uint32_t n_txn, c
     if (nt) DV_LAUNCH(k_reply_emit, nt, kBlock, 0, s, commit, n_txn, bc, txn_id, cst, rnode, o_txn_id, o_cst, o_rnode);
 }
 
+// ---- the reply mbufs packed on the device (dv_wire_respond_device): what
+// dv_wire_respond (csrc/wire.cpp) writes, from reply fields in device memory.
+// A stable multi-split of the answered txns by destination, then a closed-form
+// placement.  Per tile of kReplyTile txns the answered ones are counted per
+// destination (k_rsp_count), each destination's tiles are scanned
+// (k_rsp_scan), the destinations are scanned into their first mbuf and first
+// message and the call is decided (k_rsp_plan); rank r of destination d is
+// then message r % per of mbuf dmb[d] + r / per, and the dword it starts at is
+//   3 * (dmb[d] + r / per + 1) + kDw * (dmsg[d] + r)
+// -- every mbuf in front of it and its own carry a 12-byte header, every
+// message in front of it is kDw dwords.  The emit (k_rsp_emit*) orders a
+// tile's answered txns by (destination, rank) in LDS and walks their dwords
+// with consecutive lanes on consecutive dwords: a destination's run is
+// contiguous but for the headers, so a wave's store covers 256 contiguous
+// bytes wherever a run is that long.  out is written in whole dwords (every
+// size of the format is a multiple of 4 and out is 4-byte aligned), each once.
+namespace {
+
+static_assert(kBlock == DV_WIRE_DEST_MAX && kBlock == kReplyTile, "a thread per txn of the tile and per destination");
+
+// A dialect's reply (ClientResponseMessage / AckMessage): kDw dwords -- rtype,
+// txn_id, [batch_id,] 16 of mq_time and latencies, then client_startts or the
+// ack's rc -- and kPer of them to a full mbuf.
+struct RspClient {
+    static constexpr uint32_t kDw = 21, kType = DV_WIRE_CL_RSP;
+    static constexpr bool kCalvin = false;
+};
+struct RspCalvin {
+    static constexpr uint32_t kDw = 22, kType = DV_WIRE_CALVIN_ACK;
+    static constexpr bool kCalvin = true;
+};
+template <class R>
+constexpr uint32_t rsp_per() {
+    return (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / (R::kDw * 4);
+}
+static_assert(rsp_per<RspClient>() == 48 && rsp_per<RspCalvin>() == 46, "replies of a full mbuf");
+
+// which entries of the call are answered, and by which txn's fields
+struct RspSel {
+    uint32_t n, n_src_txn;
+    const uint8_t *commit;
+    const uint32_t *src, *rnode;
+};
+
+__device__ __forceinline__ bool rsp_answered(const RspSel &s, uint32_t i, uint32_t &txn) {
+    txn = i;
+    if (i >= s.n) return false;
+    if (s.src) {
+        txn = s.src[i];
+        return true;
+    }
+    return !s.commit || s.commit[i] != 0;
+}
+
+// dword f of a reply
+template <class R>
+__device__ __forceinline__ uint32_t rsp_dword(uint32_t f, uint64_t txn_id, uint64_t tail) {
+    // tail: CALVIN the batch id (dwords 3, 4; the rc behind the latencies is 0), else client_startts (the last two)
+    constexpr uint32_t t0 = R::kCalvin ? 3 : R::kDw - 2;
+    if (f == 0) return R::kType;
+    if (f <= 2) return (uint32_t)(txn_id >> (32 * (f - 1)));
+    if (f == t0 || f == t0 + 1) return (uint32_t)(tail >> (32 * (f - t0)));
+    return 0;
+}
+
+template <class R>
+__device__ __forceinline__ void rsp_emit(const RspSel &sel, uint32_t nt, uint32_t node_id, uint64_t batch_id,
+                                         const uint64_t *__restrict__ txn_id, const uint64_t *__restrict__ cst,
+                                         const ReplyWs &ws, uint32_t *__restrict__ out,
+                                         uint64_t *__restrict__ batch_off) {
+    constexpr uint32_t per = rsp_per<R>();
+    __shared__ uint32_t lds4[4], s_wave[4][DV_WIRE_DEST_MAX], s_first[DV_WIRE_DEST_MAX];
+    __shared__ uint64_t s_pos[kReplyTile], s_id[kReplyTile], s_tail[kReplyTile];
+    if (ws.res->status != DV_OK) return;  // (the plan refused the call: nothing is written)
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) s_wave[w][tid] = 0;
+    __syncthreads();
+    uint32_t txn;
+    const bool ans = rsp_answered(sel, blockIdx.x * kReplyTile + tid, txn);
+    const uint32_t d = ans ? sel.rnode[txn] : 0u;  // (< n_dest: the plan saw no err)
+    // the txn's place among the wave's answered txns of its destination, then among the tile's
+    const uint64_t peers = match_digit(d, __ballot(ans));
+    const uint32_t in_wave = mask_rank(peers);
+    if (ans && in_wave == 0) s_wave[wave][d] = (uint32_t)__popcll(peers);
+    __syncthreads();
+    uint32_t n_ans = 0;
+    const uint32_t first = block_excl_scan256(s_wave[0][tid] + s_wave[1][tid] + s_wave[2][tid] + s_wave[3][tid], lds4,
+                                              &n_ans);
+    s_first[tid] = first;  // destination tid's first slot in the tile's (destination, rank) order
+    __syncthreads();
+    if (ans) {
+        uint32_t in_tile = in_wave;
+        for (uint32_t w = 0; w < wave; w++) in_tile += s_wave[w][d];
+        const uint32_t r = ws.cnt[(uint64_t)d * nt + blockIdx.x] + in_tile;
+        const uint32_t j = r / per, mb = ws.dmb[d] + j;
+        const uint64_t pos = 3ull * ((uint64_t)mb + 1) + (uint64_t)R::kDw * ((uint64_t)ws.dmsg[d] + r);
+        const uint64_t id = txn_id[txn], tail = R::kCalvin ? batch_id : cst[txn];
+        if (r == j * per) {  // the mbuf's first message: its header and offset
+            const uint32_t left = ws.tot[d] - r;
+            out[pos - 3] = d;
+            out[pos - 2] = node_id;
+            out[pos - 1] = left < per ? left : per;
+            batch_off[mb] = (pos - 3) * 4;
+        }
+#ifdef DVCC_RSP_EMIT_SIMPLE
+        // the first form (A/B only): every thread its own message, a wave's stores kDw dwords apart
+        for (uint32_t f = 0; f < R::kDw; f++) out[pos + f] = rsp_dword<R>(f, id, tail);
+#else
+        const uint32_t slot = s_first[d] + in_tile;
+        s_pos[slot] = pos;
+        s_id[slot] = id;
+        s_tail[slot] = tail;
+#endif
+    }
+#ifndef DVCC_RSP_EMIT_SIMPLE
+    __syncthreads();
+    for (uint32_t i = tid; i < n_ans * R::kDw; i += kBlock) {
+        const uint32_t slot = i / R::kDw, f = i - slot * R::kDw;
+        out[s_pos[slot] + f] = rsp_dword<R>(f, s_id[slot], s_tail[slot]);
+    }
+#endif
+}
+
+}  // namespace
+
+// tile blockIdx.x: its answered txns per destination; a node or a list index out of range raises ws.err
+__global__ __launch_bounds__(kBlock) void k_rsp_count(RspSel sel, uint32_t n_dest, uint32_t nt, ReplyWs ws) {
+    __shared__ uint32_t s_cnt[DV_WIRE_DEST_MAX];
+    s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t txn;
+    if (rsp_answered(sel, blockIdx.x * kReplyTile + threadIdx.x, txn)) {
+        const uint32_t d = sel.src && txn >= sel.n_src_txn ? n_dest : sel.rnode[txn];
+        if (d < n_dest) atomicAdd(&s_cnt[d], 1u);
+        else atomicOr(ws.err, 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < n_dest) ws.cnt[(uint64_t)threadIdx.x * nt + blockIdx.x] = s_cnt[threadIdx.x];
+}
+
+// destination blockIdx.x: its tiles' counts become the replies in front of each tile
+__global__ __launch_bounds__(kBlock) void k_rsp_scan(ReplyWs ws, uint32_t nt) {
+    __shared__ uint32_t lds4[4];
+    const uint32_t tot = block_chunk_scan256(ws.cnt + (uint64_t)blockIdx.x * nt, nt, lds4);
+    if (threadIdx.x == 0) ws.tot[blockIdx.x] = tot;
+}
+
+// One workgroup, a thread per destination: the mbufs and messages in front of
+// each, the totals, and the call's fate -- decided here, before any byte of
+// out or batch_off is written (the closing offset is this kernel's).
+__global__ __launch_bounds__(kBlock) void k_rsp_plan(ReplyWs ws, uint32_t nt, uint32_t n_dest, uint32_t per,
+                                                     uint32_t msg_bytes, uint64_t cap, uint32_t max_batches,
+                                                     uint64_t *__restrict__ batch_off) {
+    __shared__ uint32_t lds4[4];
+    const uint32_t d = threadIdx.x;
+    const uint32_t c = nt && d < n_dest ? ws.tot[d] : 0u;
+    uint32_t tot_mb = 0, tot_msg = 0;
+    const uint32_t mb = block_excl_scan256(c / per + (c % per ? 1u : 0u), lds4, &tot_mb);
+    const uint32_t msg = block_excl_scan256(c, lds4, &tot_msg);
+    if (d < n_dest) {
+        ws.dmb[d] = mb;
+        ws.dmsg[d] = msg;
+    }
+    if (d != 0) return;
+    const bool bad = *ws.err != 0;
+    const uint64_t bytes = (uint64_t)tot_mb * DV_WIRE_HDR + (uint64_t)tot_msg * msg_bytes;
+    dv_wire_rsp_result r;
+    r.status = bad || bytes > cap || tot_mb > max_batches ? DV_ERR_ARG : DV_OK;
+    r.n_batches = bad ? 0u : tot_mb;
+    r.n_msgs = bad ? 0u : tot_msg;
+    r.pad_ = 0;
+    r.n_bytes = bad ? 0ull : bytes;
+    *ws.res = r;
+    if (r.status == DV_OK) batch_off[tot_mb] = bytes;  // (tot_mb == 0: batch_off[0] = 0)
+}
+
+__global__ __launch_bounds__(kBlock) void k_rsp_emit(RspSel sel, uint32_t nt, uint32_t node_id,
+                                                     const uint64_t *__restrict__ txn_id,
+                                                     const uint64_t *__restrict__ cst, ReplyWs ws,
+                                                     uint32_t *__restrict__ out, uint64_t *__restrict__ batch_off) {
+    rsp_emit<RspClient>(sel, nt, node_id, 0, txn_id, cst, ws, out, batch_off);
+}
+
+__global__ __launch_bounds__(kBlock) void k_rsp_emit_calvin(RspSel sel, uint32_t nt, uint32_t node_id,
+                                                            uint64_t batch_id, const uint64_t *__restrict__ txn_id,
+                                                            ReplyWs ws, uint32_t *__restrict__ out,
+                                                            uint64_t *__restrict__ batch_off) {
+    rsp_emit<RspCalvin>(sel, nt, node_id, batch_id, txn_id, nullptr, ws, out, batch_off);
+}
+
+static RspSel rsp_sel(const dv_wire_rsp_in &in) {
+    return RspSel{in.n, in.n_src_txn, in.commit, in.src, in.return_node};
+}
+
+void launch_rsp_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
+                     const ReplyWs &ws) {
+    const uint32_t nt = reply_tiles(in.n);
+    const uint32_t per = cfg.calvin ? rsp_per<RspCalvin>() : rsp_per<RspClient>();
+    const uint32_t msg_bytes = 4 * (cfg.calvin ? RspCalvin::kDw : RspClient::kDw);
+    (void)hipMemsetAsync(ws.err, 0, sizeof(uint32_t), s);
+    if (nt) {
+        DV_LAUNCH(k_rsp_count, nt, kBlock, 0, s, rsp_sel(in), in.n_dest, nt, ws);
+        DV_LAUNCH(k_rsp_scan, in.n_dest, kBlock, 0, s, ws, nt);
+    }
+    DV_LAUNCH(k_rsp_plan, 1, kBlock, 0, s, ws, nt, in.n_dest, per, msg_bytes, out.cap, out.max_batches, out.batch_off);
+}
+
+void launch_rsp_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
+                     const ReplyWs &ws) {
+    const uint32_t nt = reply_tiles(in.n);
+    if (!nt) return;
+    uint32_t *out32 = reinterpret_cast<uint32_t *>(out.out);
+    if (cfg.calvin)
+        DV_LAUNCH(k_rsp_emit_calvin, nt, kBlock, 0, s, rsp_sel(in), nt, cfg.node_id, in.batch_id, in.txn_id, ws, out32,
+                  out.batch_off);
+    else
+        DV_LAUNCH(k_rsp_emit, nt, kBlock, 0, s, rsp_sel(in), nt, cfg.node_id, in.txn_id, in.client_startts, ws, out32,
+                  out.batch_off);
+}
+
 }  // namespace dvcc

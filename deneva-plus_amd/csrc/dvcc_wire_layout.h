@@ -83,6 +83,32 @@ inline uint64_t wire_ws_walk(void *base_, uint32_t nb, uint32_t stride, WireWs &
     return at;
 }
 
+// The reply packer's words (dv_wire_respond_device) for nt tiles of kReplyTile
+// txns over n_dest destinations: the stable multi-split's counts, destination-
+// major so that one destination's tiles are contiguous for its scan.
+struct ReplyWs {
+    dv_wire_rsp_result *res;  // kWireResBytes
+    uint32_t *err;            // one word: an answered txn's node or a list's index out of range
+    uint32_t *tot;            // [n_dest] replies per destination
+    uint32_t *dmb, *dmsg;     // [n_dest] mbufs / messages in front of the destination's first
+    uint32_t *cnt;            // [n_dest * nt] per tile, then the destination's replies in front of the tile
+};
+static_assert(sizeof(dv_wire_rsp_result) <= kWireResBytes, "the context's pinned words");
+
+inline uint64_t reply_ws_layout(void *base_, uint32_t nt, uint32_t n_dest, ReplyWs &w) {
+    char *base = static_cast<char *>(base_);
+    uint64_t at = 0;
+    uint8_t *res;
+    wire_ws_field(base, at, res, kWireResBytes);
+    w.res = reinterpret_cast<dv_wire_rsp_result *>(res);
+    wire_ws_field(base, at, w.err, 1);
+    wire_ws_field(base, at, w.tot, n_dest);
+    wire_ws_field(base, at, w.dmb, n_dest);
+    wire_ws_field(base, at, w.dmsg, n_dest);
+    wire_ws_field(base, at, w.cnt, (uint64_t)n_dest * (nt ? nt : 1));
+    return at;
+}
+
 inline uint64_t wire_ws_layout(void *base, uint32_t nb, WireWs &w) {
     return wire_ws_walk(base, nb, kWireMaxMsg, w, nullptr);
 }

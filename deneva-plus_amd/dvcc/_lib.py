@@ -175,6 +175,26 @@ class WireCalvinPos(ctypes.Structure):  # dv_wire_calvin_pos: cursor and epoch t
                 ("max_txn_acc", ctypes.c_uint32), ("stop", ctypes.c_uint32)]
 
 
+WIRE_DEST_MAX = 256
+
+
+class WireRspIn(ctypes.Structure):  # dv_wire_rsp_in: the reply fields dv_wire_respond_device packs
+    _fields_ = [("n", ctypes.c_uint32), ("n_dest", ctypes.c_uint32), ("commit", ctypes.c_void_p),
+                ("src", ctypes.c_void_p), ("n_src_txn", ctypes.c_uint32), ("pad_", ctypes.c_uint32),
+                ("txn_id", ctypes.c_void_p), ("client_startts", ctypes.c_void_p), ("return_node", ctypes.c_void_p),
+                ("batch_id", ctypes.c_uint64)]
+
+
+class WireRspOut(ctypes.Structure):  # dv_wire_rsp_out: its device output buffers
+    _fields_ = [("out", ctypes.c_void_p), ("cap", ctypes.c_uint64), ("batch_off", ctypes.c_void_p),
+                ("max_batches", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class WireRspResult(ctypes.Structure):  # dv_wire_rsp_result
+    _fields_ = [("status", ctypes.c_int32), ("n_batches", ctypes.c_uint32), ("n_msgs", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32), ("n_bytes", ctypes.c_uint64)]
+
+
 # dv_wire_calvin_pos::stop (DV_WIRE_STOP_*)
 WIRE_STOP_END, WIRE_STOP_BATCH, WIRE_STOP_CAPACITY, WIRE_STOP_WINDOW, WIRE_STOP_MALFORMED, WIRE_STOP_STALE = range(6)
 WIRE_NO_BATCH_ID = (1 << 64) - 1
@@ -305,6 +325,7 @@ SIGNATURES = [
                                                          _P(WireTpccDevOut), _P(WireCalvinPos)]),
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
+    ("dv_wire_respond_device", ctypes.c_int, [_vp, _P(WireCfg), _P(WireRspIn), _P(WireRspOut), _P(WireRspResult)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
     ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
     ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),

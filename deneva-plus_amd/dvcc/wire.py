@@ -15,7 +15,10 @@ CALVIN sequencer streams (dv_wire_ingest_device_calvin, YCSB): cut at the
 message where the batch id changes, appended stream by stream in node order;
 CalvinTpccDeviceWireIngress the same streams of TPC-C queries
 (dv_wire_ingest_device_calvin_tpcc).  No combination of workload and CALVIN is
-left on the host decoder.
+left on the host decoder.  The device ingresses also answer on the device:
+respond_device / respond_logged_device pack the reply mbufs there
+(dv_wire_respond_device) and return device tensors; reply_batches slices a
+host copy of them into respond's list of batches.
 """
 import ctypes
 from dataclasses import dataclass
@@ -61,6 +64,19 @@ def _pack_replies(cfg, n, batch_id, txn_id, client_startts, return_node, commit)
     L.check(L.lib().dv_wire_respond(ctypes.byref(cfg), ctypes.byref(e), _ptr(commit), _ptr(out), len(out),
                                     _ptr(off), max_b, ctypes.byref(nb)), "dv_wire_respond")
     return [out[int(off[b]):int(off[b + 1])].tobytes() for b in range(nb.value)]
+
+
+def reply_batches(out, batch_off, n_batches):
+    """What respond_device / respond_logged_device return (device tensors, or
+    host copies of them) as the list of batches (bytes) respond returns.
+    Device tensors are copied once the device is idle: they are written on
+    the engine's stream, which torch's copy does not wait for."""
+    if getattr(out, "is_cuda", False):
+        import torch
+        torch.cuda.synchronize()
+    h = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)  # noqa: E731
+    buf, off = h(out).view(np.uint8), h(batch_off).view(np.uint64)
+    return [buf[int(off[b]):int(off[b + 1])].tobytes() for b in range(n_batches)]
 
 
 class WireIngress:
@@ -205,6 +221,36 @@ class _DeviceIngress:
         if rc not in (L.DV_OK, L.WIRE_MORE, L.DV_ERR_ARG) or not launched:
             L.check(rc, what)
 
+    n_dest = L.WIRE_DEST_MAX  # every return node lies below it (set it lower for smaller reply buffers)
+
+    def _respond_device(self, n, commit, src, n_src_txn, txn_id, client_startts, return_node, batch_id=None):
+        """dv_wire_respond_device over device reply fields -> (out, batch_off,
+        n_batches): the reply mbufs back to back in a uint8 device tensor, batch
+        b at out[batch_off[b]:batch_off[b + 1]] (int64 device tensor).  The
+        tensors are the ingress's own, sized for n replies to n_dest
+        destinations and written on the engine's stream: the next call
+        overwrites them."""
+        import torch
+        calvin = bool(self.cfg.calvin)
+        msg = 4 + 8 + (8 if calvin else 0) + 8 + 7 * 8 + (4 if calvin else 8)
+        max_b = n // ((L.WIRE_MSG_MAX - L.WIRE_HDR) // msg) + self.n_dest + 1
+        cap = max_b * L.WIRE_HDR + n * msg
+        if getattr(self, "_rsp_out", None) is None or self._rsp_out.numel() < cap:
+            self._rsp_out = self._new(cap, torch.uint8)
+        if getattr(self, "_rsp_off", None) is None or self._rsp_off.numel() < max_b + 1:
+            self._rsp_off = self._new(max_b + 1, torch.int64)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rin = L.WireRspIn(n, self.n_dest, p(commit), p(src), n_src_txn, 0, p(txn_id), p(client_startts),
+                          p(return_node), L.WIRE_NO_BATCH_ID if batch_id is None else batch_id)
+        rout = L.WireRspOut(self._rsp_out.data_ptr(), cap, self._rsp_off.data_ptr(), max_b, 0)
+        res = L.WireRspResult(status=1)
+        self.engine._after_torch()
+        rc = L.lib().dv_wire_respond_device(self.engine._ctx, ctypes.byref(self.cfg), ctypes.byref(rin),
+                                            ctypes.byref(rout), ctypes.byref(res))
+        L.check(rc, "dv_wire_respond_device")  # (a return node at or above n_dest: DV_ERR_ARG)
+        self._rsp_held = (commit, src)  # (the emit may still read them when this returns)
+        return self._rsp_out[:res.n_bytes], self._rsp_off[:res.n_batches + 1], res.n_batches
+
     def _with_replies(self, ep, n):
         """ep with the device reply arrays of its n txns"""
         ep.txn_id, ep.client_startts, ep.return_node = self.txn_id[:n], self.client_startts[:n], self.return_node[:n]
@@ -231,6 +277,21 @@ class _DeviceReplies(_DeviceIngress):
                                                     tid.data_ptr(), cst.data_ptr(), rn.data_ptr(),
                                                     ctypes.byref(cnt)), "dv_wire_reply_fields_device")
         return self._pack(tid, cst, rn, cnt.value)
+
+    def respond_device(self, ep, d_commit):
+        """respond's batches packed on the device (dv_wire_respond_device):
+        (out, batch_off, n_batches) as _respond_device returns them --
+        reply_batches(out, batch_off, n_batches) is respond(ep, d_commit)."""
+        return self._respond_device(ep.n_txn, d_commit, None, 0, ep.txn_id, ep.client_startts, ep.return_node)
+
+    def respond_logged_device(self, src):
+        """respond_logged's batches packed on the device: the reply fields of
+        the epoch this ingress decoded last are read through `src` by the
+        packer itself, in list order."""
+        import torch
+        idx = src.to(device=self.txn_id.device, dtype=torch.int32).contiguous()
+        return self._respond_device(int(idx.numel()), None, idx, self.max_txn, self.txn_id, self.client_startts,
+                                    self.return_node)
 
     def _pack(self, tid, cst, rn, c):
         """the host packer (dv_wire_respond) over the first c entries of device
@@ -474,6 +535,12 @@ class _CalvinStreams(_DeviceIngress):
         self.engine._after_torch()
         return _pack_replies(self.cfg, n, ep.batch_id, ep.txn_id.cpu().numpy().view(np.uint64), None,
                              ep.return_node.cpu().numpy().view(np.uint32), None)
+
+    def respond_device(self, ep):
+        """respond's batches packed on the device (dv_wire_respond_device):
+        (out, batch_off, n_batches) as _respond_device returns them --
+        reply_batches(out, batch_off, n_batches) is respond(ep)."""
+        return self._respond_device(ep.n_txn, None, None, 0, ep.txn_id, None, ep.return_node, ep.batch_id)
 
 
 class CalvinDeviceWireIngress(_CalvinStreams):

@@ -65,6 +65,8 @@
  *   dv_wire_ingest_device_calvin_tpcc / their batch ids: no combination is left on the host
  *   dv_wire_reply_fields_device decoder); the committed txns' reply fields compacted for
  *                               dv_wire_respond
+ *   dv_wire_respond_device      dv_wire_respond's mbufs packed on the device from reply
+ *                               fields in device memory (same reference lines)
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
  * the final table state equal a single worker thread running the same epoch
@@ -1426,6 +1428,70 @@ int dv_wire_reply_fields_device(dv_ctx *ctx, const uint8_t *commit, uint32_t n_t
                                 const uint64_t *client_startts, const uint32_t *return_node,
                                 uint64_t *out_txn_id, uint64_t *out_client_startts, uint32_t *out_return_node,
                                 uint32_t *n_out);
+/* ---- The reply mbufs packed on the device (dvcc_wire.hip): dv_wire_respond's
+ * output -- CL_RSP batches to the clients (worker_thread.cpp:152;
+ * ClientResponseMessage, message.cpp:921-949) or, under CALVIN, CALVIN_ACK
+ * batches to the sequencers (worker_thread.cpp:127-136; AckMessage,
+ * message.cpp:1057-1110) -- from reply fields in device memory into device
+ * bytes, so an epoch ingested and decided on the device is answered there. */
+#define DV_WIRE_DEST_MAX 256    /* return nodes a call may name */
+
+typedef struct dv_wire_rsp_in {
+    uint32_t n;                    /* txns looked at (src == NULL) or entries of src          */
+    uint32_t n_dest;               /* every return node < n_dest; 1 .. DV_WIRE_DEST_MAX       */
+    const uint8_t *commit;         /* device [n], or NULL: every txn is answered (CALVIN; a log slice) */
+    const uint32_t *src;           /* device [n] or NULL: entry i answers txn src[i] of the arrays below,
+                                      in list order (a commit log's slice); with src, commit must be NULL */
+    uint32_t n_src_txn, pad_;      /* with src: every src[i] < n_src_txn                      */
+    const uint64_t *txn_id;        /* device                                                  */
+    const uint64_t *client_startts;/* device; NULL under CALVIN                               */
+    const uint32_t *return_node;   /* device                                                  */
+    uint64_t batch_id;             /* CALVIN: every ack's                                     */
+} dv_wire_rsp_in;
+
+typedef struct dv_wire_rsp_out {
+    uint8_t *out;                  /* device (or host-mapped) bytes, 4-byte aligned           */
+    uint64_t cap;
+    uint64_t *batch_off;           /* device (or host-mapped) u64[max_batches + 1]            */
+    uint32_t max_batches, pad_;
+} dv_wire_rsp_out;
+
+typedef struct dv_wire_rsp_result {
+    int32_t status;                /* what the call returns: DV_OK or DV_ERR_ARG              */
+    uint32_t n_batches;
+    uint32_t n_msgs;               /* txns answered                                           */
+    uint32_t pad_;
+    uint64_t n_bytes;
+} dv_wire_rsp_result;
+
+/* On DV_OK out[0 .. n_bytes), batch_off[0 .. n_batches] and n_batches equal
+ * what dv_wire_respond writes for the same cfg, fields and commit bytes, bit
+ * for bit (with src: for the fields gathered in list order and all-ones commit
+ * bytes): destinations ascending, a destination's messages in txn (list)
+ * order, a message 84 bytes (CL_RSP) or 88 (CALVIN_ACK), (4096 - 12) / that
+ * -- 48 or 46 -- to a full mbuf, no mbuf for a destination without a reply,
+ * latency fields and the ack's rc 0, batch_off[0] = 0.  Commit bytes, when
+ * given, select the answered txns under CALVIN too (dv_wire_respond
+ * acknowledges every txn whatever they hold: NULL gives its output).  Nothing
+ * is written at or past out[n_bytes] or batch_off[n_batches + 1].
+ * DV_ERR_ARG in res->status when the bytes exceed cap, the mbufs exceed
+ * max_batches, an answered txn's return node is >= n_dest or a src[i] is >=
+ * n_src_txn: decided before the emit, so no byte of out or batch_off is
+ * written (the host packer writes the mbufs in front of the one that does not
+ * fit: the one difference); n_bytes / n_batches / n_msgs then hold what the
+ * replies need in the first two cases and 0 in the last two.  n == 0: DV_OK,
+ * no batch.
+ * Queued on the context's stream; the call waits for the result record alone,
+ * as the ingests do, and what reads out afterwards on the same stream needs no
+ * other synchronisation.
+ * Refused before any launch (DV_ERR_ARG, *res untouched): a null pointer among
+ * ctx, cfg, in, out, res, out->out, out->batch_off, txn_id, return_node;
+ * client_startts NULL when not CALVIN; commit and src both given; n_dest
+ * outside 1 .. DV_WIRE_DEST_MAX; out->out not 4-byte aligned; zero node_cnt.
+ * A context in the middle of an epoch: DV_ERR_STATE. */
+int dv_wire_respond_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_rsp_in *in,
+                           const dv_wire_rsp_out *out, dv_wire_rsp_result *res);
+
 /* 1 when an epoch of n_txn txns given as records and boundaries alone
  * (recs32, txn_begin, n_acc_dev) would take this context's tb-mode
  * prefix-kill path, which reads nothing else; 0 when it also needs keys /
