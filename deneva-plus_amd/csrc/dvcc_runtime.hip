@@ -168,8 +168,9 @@ struct dv_ctx {
     // (RefillBackoff); lost_seen: that count as the last loop call read it.
     // Under decision lanes the ring, the wait partials and the lost count are
     // lanes[0]'s, and every lane brings its own plan words and block counts
-    // (backoff_at).  tpcc: attached through dv_tpcc_closed_loop_backoff, for
-    // the TPC-C loop, which takes no other attachment.
+    // (backoff_at).  tpcc: attached through dv_tpcc_closed_loop_backoff or
+    // dv_tpcc_closed_loop_backoff_lanes, for the TPC-C loops, which take no
+    // other attachment (and each only the one for its lane count).
     struct LoopBo {
         bool on = false;
         bool tpcc = false;
@@ -3367,7 +3368,8 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *c, const dv_epoch_dev *pool, const uin
     if (!c || !pool_args || !buf_args || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
     if (c->phase != 0) return DV_ERR_STATE;
     if (c->cfg.cc_alg == DV_CALVIN || c->comm) return DV_ERR_STATE;
-    if (c->bo.on && !c->bo.tpcc) return DV_ERR_STATE;  // (a ring attached for the YCSB loops)
+    // (a ring attached for the YCSB loops, or for the TPC-C lanes loop)
+    if (c->bo.on && (!c->bo.tpcc || c->bo.lanes != 1)) return DV_ERR_STATE;
     uint64_t bound = 0;
     int r = loop_check(c, pool, pool_begin, cursor, n_txn, bufs, 2, buf_cap, n_epochs, true, &bound);
     if (!r && (!buf_args[0] || !buf_args[1])) r = DV_ERR_ARG;
@@ -3484,6 +3486,116 @@ int dv_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const
     return r ? r : backoff_lost(c0);
 }
 
+// The TPC-C closed loop over decision lanes: dv_epoch_run_closed_loop_lanes'
+// order of things -- epoch k on lanes[k % L], lane l's buffers 2l and 2l + 1,
+// refill k queued behind execution k inside the lanes' execution order, the
+// shared cursor, tracker and ring (lanes[0]'s) -- with
+// dv_tpcc_epoch_run_closed_loop's epochs: table bytes and operation words in
+// every refill.  Epochs are queued as dv_tpcc_epoch_run_device_lanes queues
+// them, except that only the decision replays from a graph: the execution, the
+// order words and the refill (whose k, k_next and buffers change every epoch)
+// are queued behind it, outside.  The graph's key names the buffer and its
+// operation words (graph_decide: ep, args).
+int dv_tpcc_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const dv_epoch_dev *pool,
+                                        const uint64_t *pool_args, const uint32_t *pool_begin, uint32_t *cursor,
+                                        uint32_t n_txn, dv_epoch_dev *bufs, uint64_t *const *buf_args,
+                                        uint64_t buf_cap, uint32_t n_epochs, int resume, uint8_t *const *d_commits,
+                                        uint64_t *const *d_oids, dv_stats *sts) {
+    int r = check_lanes(lanes, n_lanes);
+    if (r) return r;
+    if (n_lanes == 1)
+        return dv_tpcc_epoch_run_closed_loop(lanes[0], pool, pool_args, pool_begin, cursor, n_txn, bufs, buf_args,
+                                             buf_cap, n_epochs, resume, d_commits, d_oids, sts);
+    dv_ctx *const c0 = lanes[0];
+    KProfScope kps_(c0);  // (DV_FLAG_KERNEL_PROFILE on lanes[0]: every lane's refill launches are timed into it)
+    if (!pool_args || !buf_args || c0->cfg.workload != DV_TPCC) return DV_ERR_ARG;
+    if (c0->cfg.cc_alg == DV_CALVIN) return DV_ERR_STATE;
+    // a back-off: lanes[0]'s, attached for this loop and lane count (dv_tpcc_closed_loop_backoff_lanes)
+    if (c0->bo.on && (!c0->bo.tpcc || c0->bo.lanes != n_lanes)) return DV_ERR_STATE;
+    for (uint32_t l = 0; l < n_lanes; l++)
+        if ((l && lanes[l]->bo.on) || lanes[l]->comm) return DV_ERR_STATE;
+    uint64_t bound = 0;
+    r = loop_check(c0, pool, pool_begin, cursor, n_txn, bufs, 2 * n_lanes, buf_cap, n_epochs, true, &bound);
+    for (uint32_t b = 0; !r && b < 2 * n_lanes; b++)
+        if (!buf_args[b]) r = DV_ERR_ARG;
+    if (r) return r;
+    HIPCHK(hipSetDevice(c0->cfg.device));
+    for (uint32_t l = 0; l < n_lanes; l++) {
+        r = carry_bufs(lanes[l], carry_blocks(n_txn));
+        if (!r) r = backoff_bufs(lanes[l], carry_blocks(n_txn), c0->bo.on);
+        if (r) return r;
+    }
+    const LoopForm form{};
+    const RefillReq req = loop_refill(pool, pool_args, pool_begin, cursor, n_txn, bound, form);
+    // (as dv_epoch_run_closed_loop_lanes: epoch k in buffer 2l + (j & 1), k = j * L + l)
+    auto buf_i = [&](uint32_t k, uint32_t ahead) { return 2 * (k % n_lanes) + (((k / n_lanes) + ahead) & 1); };
+    RefillTrack tw;
+    RefillBackoff bw;
+    auto desc = [&](uint32_t k) { return loop_desc(bufs[buf_i(k, 0)], form, pool, n_txn, bound); };
+    auto commit_of = [&](uint32_t k) { return d_commits ? d_commits[k] : nullptr; };
+    auto oid_of = [&](uint32_t k) { return d_oids ? d_oids[k] : nullptr; };
+    // behind epoch k's execution on its lane c (a no-op when k halted)
+    auto refill = [&](dv_ctx *c, uint32_t k) {
+        const uint32_t ib = buf_i(k, 0), ob = buf_i(k, 1);
+        return enqueue_refill(c, req, form, &bufs[ib], bufs[ob],
+                              track_at(c0, true, k, k + n_lanes, ib, ob, n_lanes, &tw),
+                              backoff_at(c0, c, ib, ob, &bw), buf_args[ib], buf_args[ob]);
+    };
+    if (!resume)  // each lane's first epoch: fresh txns (and what an attached ring releases), in lane order
+        for (uint32_t l = 0; l < n_lanes; l++) {
+            dv_ctx *c = lanes[l];
+            const uint32_t ob = buf_i(l, 0);
+            r = enqueue_refill(c, req, form, nullptr, bufs[ob], track_at(c0, false, 0, l, 0, ob, n_lanes, &tw),
+                               backoff_at(c0, c, ob, ob, &bw), nullptr, buf_args[ob]);
+            if (r) return r;
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+    // An epoch is queued ahead only when its decision is all launches: round 0
+    // and the asynchronous launch (round0_then_async -- 32-bit round elements,
+    // asynchronous rounds on; epoch_setup's stride).  decide_epoch takes that
+    // form up to kAsyncSmallAcc accesses, but a loop epoch's n_acc is the
+    // bound n_txn * max_txn_acc, not its size (config E: 2.16M for some 0.85M
+    // accesses), so the form is taken here whatever the bound: the try itself
+    // declines on the device when the live set does not fit, which halts the
+    // epoch, and run_lanes decides it again synchronously.  Any other context
+    // runs its epochs one at a time, each with its refill.
+    uint32_t slog = 4;
+    while ((1u << slog) < pool->max_txn_acc) slog++;
+    bool pipelined = round_el32(n_txn, slog);
+    for (uint32_t l = 0; l < n_lanes; l++)  // (every lane: a timing flag on one of them records its events per epoch)
+        pipelined = pipelined && !timing(lanes[l]) && !ktiming(lanes[l]) && lanes[l]->async_g &&
+                    !(lanes[l]->cfg.flags & (DV_FLAG_NO_ASYNC | DV_FLAG_EL64));
+    r = run_lanes(
+        lanes, n_lanes, n_epochs, sts, commit_of, [&](uint32_t) { return pipelined; },
+        [&](dv_ctx *c, uint32_t k, auto &tail) {
+            const dv_epoch_dev d = desc(k);
+            const uint64_t *args = buf_args[buf_i(k, 0)];
+            const int e = graph_decide(c, &d, args, [&] {
+                int rr = dv_tpcc_epoch_begin(c, &d, args, oid_of(k));
+                if (!rr && !c->el32) rr = DV_ERR_STATE;  // (pipelined says otherwise)
+                if (!rr) {
+                    round0_then_async(c);
+                    rr = hip_fail(hipGetLastError(), "rounds");
+                }
+                return rr;
+            });
+            return e ? e : tail();
+        },
+        refill,
+        [&](uint32_t k, dv_stats *st) {  // (synchronous, refill included: the next refill, on
+                                         // another lane, draws from the cursor after it)
+            dv_ctx *c = lanes[k % n_lanes];
+            const dv_epoch_dev d = desc(k);
+            int e = dv_tpcc_epoch_run_device(c, &d, buf_args[buf_i(k, 0)], commit_of(k), oid_of(k), st);
+            if (!e) e = refill(c, k);
+            if (!e) e = hip_fail(hipStreamSynchronize(c->stream), "sync");
+            return e;
+        });
+    for (uint32_t l = 0; l < n_lanes; l++) (void)hipStreamSynchronize(lanes[l]->stream);
+    if (!r && c0->trk.on) c0->trk.next += n_epochs;
+    return r ? r : backoff_lost(c0);
+}
+
 int dv_closed_loop_track(dv_ctx *c, const dv_loop_track *trk) {
     if (!c) return DV_ERR_ARG;
     if (!trk) {
@@ -3537,13 +3649,18 @@ int dv_closed_loop_backoff_lanes(dv_ctx *c, const dv_loop_backoff *bo, uint32_t 
 
 int dv_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) { return dv_closed_loop_backoff_lanes(c, bo, 1); }
 
-// the same ring for dv_tpcc_epoch_run_closed_loop: the attachment says which
-// loop it is for
-int dv_tpcc_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) {
+// the same ring for the TPC-C loops (dv_tpcc_epoch_run_closed_loop at
+// n_lanes 1, dv_tpcc_epoch_run_closed_loop_lanes above it): the attachment
+// says which loop it is for, and for how many lanes
+int dv_tpcc_closed_loop_backoff_lanes(dv_ctx *c, const dv_loop_backoff *bo, uint32_t n_lanes) {
     if (!c || c->cfg.workload != DV_TPCC) return DV_ERR_ARG;
-    const int r = dv_closed_loop_backoff_lanes(c, bo, 1);
+    const int r = dv_closed_loop_backoff_lanes(c, bo, n_lanes);
     if (!r) c->bo.tpcc = bo != nullptr;
     return r;
+}
+
+int dv_tpcc_closed_loop_backoff(dv_ctx *c, const dv_loop_backoff *bo) {
+    return dv_tpcc_closed_loop_backoff_lanes(c, bo, 1);
 }
 
 }  // extern "C"

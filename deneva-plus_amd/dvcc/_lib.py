@@ -331,6 +331,10 @@ SIGNATURES = [
     ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
     ("dv_closed_loop_backoff_lanes", ctypes.c_int, [_vp, _P(LoopBackoffDesc), ctypes.c_uint32]),
     ("dv_tpcc_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),
+    ("dv_tpcc_epoch_run_closed_loop_lanes", ctypes.c_int,
+     [_P(_vp), ctypes.c_uint32, _P(EpochDev), _vp, _vp, _vp, ctypes.c_uint32, _P(EpochDev), _P(_vp), ctypes.c_uint64,
+      ctypes.c_uint32, ctypes.c_int, _P(_vp), _P(_vp), _P(Stats)]),
+    ("dv_tpcc_closed_loop_backoff_lanes", ctypes.c_int, [_vp, _P(LoopBackoffDesc), ctypes.c_uint32]),
 ]
 
 _lib = None

@@ -85,28 +85,39 @@ class TpccLoopBufs(ClosedLoopBufs):
 
 
 class TpccLoopBackoff(LoopBackoff):
-    """Exponential back-off for the TPC-C closed loop
-    (dv_tpcc_closed_loop_backoff): LoopBackoff over a LoopTrack of two
-    buffers, attached to a TpccEngine through the entry its loop accepts.  A
-    released txn's accesses come from the pool again with their table bytes
-    and operation words.  swap() goes with TpccLoopBufs.swap and
-    LoopTrack.swap after a call of n_epochs odd."""
+    """Exponential back-off for the TPC-C closed loops
+    (dv_tpcc_closed_loop_backoff, dv_tpcc_closed_loop_backoff_lanes):
+    LoopBackoff over a LoopTrack of two buffers (TpccEngine.closed_loop) or of
+    2 L (TpccEngine.closed_loop_lanes over L contexts: one ring, shared by the
+    lanes), attached to a TpccEngine -- the first of the lanes -- through the
+    entry its loop accepts.  A released txn's accesses come from the pool
+    again with their table bytes and operation words.  swap() (the single
+    loop only) goes with TpccLoopBufs.swap and LoopTrack.swap after a call of
+    n_epochs odd.  lanes says which loop the ring is for: a tracker of any
+    other size than 2 * lanes is a ValueError (the single loop's ring is never
+    built over a lanes tracker by accident)."""
 
-    def __init__(self, track, n_slots, slot_cap=None, device="cuda"):
-        if track.n_bufs != 2:
-            raise ValueError("TpccLoopBackoff: a tracker of two buffers")
+    def __init__(self, track, n_slots, slot_cap=None, device="cuda", lanes=1):
+        if lanes < 1 or track.n_bufs != 2 * lanes:
+            raise ValueError("TpccLoopBackoff: a tracker of two buffers, or of 2 * lanes with lanes=")
         super().__init__(track, n_slots, slot_cap, device)
 
+    def _entry(self, desc):
+        if self.n_lanes == 1:
+            L.check(L.lib().dv_tpcc_closed_loop_backoff(self.engine._ctx, desc), "dv_tpcc_closed_loop_backoff")
+        else:
+            L.check(L.lib().dv_tpcc_closed_loop_backoff_lanes(self.engine._ctx, desc, self.n_lanes),
+                    "dv_tpcc_closed_loop_backoff_lanes")
+
     def _attach(self):
-        arr = (ctypes.c_void_p * 2)(*[int(t.data_ptr()) for t in self.aborts])
+        arr = (ctypes.c_void_p * len(self.aborts))(*[int(t.data_ptr()) for t in self.aborts])
         d = L.LoopBackoffDesc(self.n_slots, self.slot_cap, self.park_ids.data_ptr(), self.park_aborts.data_ptr(),
                               self.slot_count.data_ptr(), arr, self.ctr.data_ptr())
-        L.check(L.lib().dv_tpcc_closed_loop_backoff(self.engine._ctx, ctypes.byref(d)),
-                "dv_tpcc_closed_loop_backoff")
+        self._entry(ctypes.byref(d))
 
     def detach(self):
         if self.engine is not None:
-            L.check(L.lib().dv_tpcc_closed_loop_backoff(self.engine._ctx, None), "dv_tpcc_closed_loop_backoff")
+            self._entry(None)
             self.engine._backoff = None
             self.engine = None
 
@@ -225,6 +236,40 @@ class TpccEngine(CCEngine):
                                                       n_epochs, int(resume), _commit_ptrs(d_commits, n),
                                                       _commit_ptrs(d_oids, n), sts),
                 "dv_tpcc_epoch_run_closed_loop")
+        if track is not None:
+            track.done += n_epochs
+        return list(sts)[:n_epochs], bufs, cursor
+
+    def closed_loop_lanes(self, lanes, pool, pool_args, pool_begin, n_txn, n_epochs, cursor=None, bufs=None,
+                          d_commits=None, d_oids=None, resume=False, track=None):
+        """dv_tpcc_epoch_run_closed_loop_lanes over [self] + lanes
+        (open_lane): epoch k on context k % L, each context's epochs a TPC-C
+        closed loop of their own (aborted txns, with their operation words,
+        retried L epochs later), the pool cursor shared, executions in epoch
+        order.  bufs: one TpccLoopBufs per context (allocated when None).
+        track: a LoopTrack of 2 L buffers attached to this engine (with a
+        TpccLoopBackoff built over it and attached too, a txn's a-th abort
+        costs L - 1 + min(2^(a-1), D) epochs).  Returns (stats list, bufs,
+        cursor); resume needs the previous call's n_epochs to be a multiple
+        of 2 L."""
+        ctxs = [self] + list(lanes)
+        nl = len(ctxs)
+        track = self._tracked(track, n_txn, 2 * nl)
+        cursor, sts = self._loop_state(pool, cursor, n_epochs)
+        if bufs is None:
+            bufs = [TpccLoopBufs(n_txn * pool.max_txn_acc, pool.keys.device) for _ in range(nl)]
+        arr = (L.EpochDev * (2 * nl))(*[b.desc(i) for b in bufs for i in range(2)])
+        bargs = [t for b in bufs for t in (getattr(b, "args", None) or [None, None])]
+        aps = (ctypes.c_void_p * (2 * nl))(*[(int(t.data_ptr()) if t is not None else None) for t in bargs])
+        lp = (ctypes.c_void_p * nl)(*[e._ctx.value for e in ctxs])
+        n = len(sts)
+        for e in ctxs:
+            e._after_torch()
+        L.check(L.lib().dv_tpcc_epoch_run_closed_loop_lanes(lp, nl, ctypes.byref(pool.desc()), _ptr(pool_args),
+                                                            _ptr(pool_begin), _ptr(cursor), n_txn, arr, aps,
+                                                            bufs[0].cap, n_epochs, int(resume),
+                                                            _commit_ptrs(d_commits, n), _commit_ptrs(d_oids, n), sts),
+                "dv_tpcc_epoch_run_closed_loop_lanes")
         if track is not None:
             track.done += n_epochs
         return list(sts)[:n_epochs], bufs, cursor

@@ -955,7 +955,8 @@ int dv_tpcc_epoch_carry(dv_ctx *ctx, const dv_epoch_dev *ep, const uint64_t *d_a
  * (tests/test_tpcc_closed_loop.py).  A tracker (dv_closed_loop_track,
  * n_bufs == 2) is taken as the YCSB loop takes it; a back-off only when it was
  * attached through dv_tpcc_closed_loop_backoff (below) -- one attached through
- * dv_closed_loop_backoff or dv_closed_loop_backoff_lanes is DV_ERR_STATE
+ * dv_closed_loop_backoff or dv_closed_loop_backoff_lanes, or through
+ * dv_tpcc_closed_loop_backoff_lanes with n_lanes > 1, is DV_ERR_STATE
  * before any launch, with cursor, tracker, ring and counters untouched.  With
  * a back-off the call returns DV_ERR_ARG after its last epoch when ring
  * entries were lost (capacity exceeded), as dv_epoch_run_closed_loop does. */
@@ -987,6 +988,74 @@ int dv_tpcc_epoch_run_closed_loop(dv_ctx *ctx, const dv_epoch_dev *pool, const u
  * parked and built exactly once.  Without a back-off the loop launches exactly
  * what it launched before. */
 int dv_tpcc_closed_loop_backoff(dv_ctx *ctx, const dv_loop_backoff *bo);   /* NULL detaches */
+
+/* The TPC-C closed loop over decision lanes: dv_epoch_run_closed_loop_lanes'
+ * order of things with dv_tpcc_epoch_run_closed_loop's epochs (lanes as for
+ * dv_tpcc_epoch_run_device_lanes, 2..8; n_lanes == 1 is
+ * dv_tpcc_epoch_run_closed_loop exactly).  Epoch k is decided on
+ * lanes[k % L], L = n_lanes; bufs / buf_args hold 2 L entries, lane l's pair
+ * at 2l, 2l + 1.  Epoch k + L is epoch k's aborted txns -- in sequence order,
+ * renumbered from 0, with their table bytes and operation words -- then fresh
+ * txns from `pool` (pool->tables, pool_args) at the shared cursor; each refill
+ * leaves the next epoch's access count in that buffer's n_acc_dev and is a
+ * no-op behind a halted or failed epoch.  Executions -- the table updates,
+ * every committed NewOrder's o_id into d_oids[k], and the refills drawing on
+ * the cursor -- run strictly in epoch order, while the lanes' decisions
+ * overlap.  Without resume the call's first L epochs are drawn fresh, lane 0
+ * first; resume continues a call whose n_epochs was a multiple of 2 L (every
+ * lane's next epoch is then in its first buffer).  The result is one sequence
+ * of epochs in which an aborted txn returns L epochs later, bit for bit:
+ * commit bytes, o_ids, stats, cursor, every table column, and each lane's
+ * next epoch with its five arrays.  A halted epoch and everything queued
+ * behind it are decided again synchronously, in order, each with its refill:
+ * every epoch is parked and built exactly once.  Epochs are queued ahead of
+ * their read-backs when every lane decides with round 0 and one asynchronous
+ * launch (32-bit round elements, no DV_FLAG_NO_ASYNC / DV_FLAG_EL64, no
+ * timing flags) -- taken here whatever the access bound n_txn *
+ * pool->max_txn_acc, the launch declining on the device, and so halting the
+ * epoch, when the live set does not fit; any other context runs its epochs
+ * one at a time, with the same results.  Only an epoch's decision may
+ * replay from a captured graph (its key names the buffer and its operation
+ * words); the execution, the refill, the tracker and the back-off launches
+ * stay outside any graph.
+ * A tracker (dv_closed_loop_track on lanes[0], n_bufs == 2 L) is taken as
+ * dv_epoch_run_closed_loop_lanes takes it, shared: retries are
+ * (k - born) / L.  A back-off only when it was attached to lanes[0] through
+ * dv_tpcc_closed_loop_backoff_lanes with this call's n_lanes.
+ * Refused before any launch, with cursor, tracker, ring and counters
+ * untouched: a context that is not DV_TPCC, a NULL pool_args / buf_args or
+ * entry of it, and what dv_tpcc_epoch_run_closed_loop's argument checks refuse
+ * (DV_ERR_ARG; a tracker whose n_bufs != 2 L or without room for n_epochs
+ * among them); CALVIN, a communicator on any lane, a lane inside an epoch
+ * (DV_ERR_STATE); a ring attached through dv_closed_loop_backoff,
+ * dv_closed_loop_backoff_lanes or dv_tpcc_closed_loop_backoff, for another
+ * lane count, or to a lane other than lanes[0] (DV_ERR_STATE).  With a
+ * back-off the call returns DV_ERR_ARG after its last epoch when ring entries
+ * were lost, from one 8-byte read. */
+int dv_tpcc_epoch_run_closed_loop_lanes(dv_ctx *const *lanes, uint32_t n_lanes, const dv_epoch_dev *pool,
+        const uint64_t *pool_args, const uint32_t *pool_begin, uint32_t *cursor, uint32_t n_txn,
+        dv_epoch_dev *bufs, uint64_t *const *buf_args, uint64_t buf_cap, uint32_t n_epochs, int resume,
+        uint8_t *const *d_commits, uint64_t *const *d_oids, dv_stats *sts);
+
+/* Exponential back-off for the TPC-C closed loop over decision lanes
+ * (dv_tpcc_epoch_run_closed_loop_lanes, L = n_lanes > 1), attached to
+ * lanes[0] on top of its tracker (n_bufs == 2 L; bo->aborts: 2 L entries).
+ * The rule is dv_closed_loop_backoff_lanes' word for word -- after epoch k an
+ * aborted txn with a = aborts + 1 parks in slot
+ * (k + L - 1 + min(2^(a-1), D)) % D; epoch e = k + L releases slot e % D and
+ * spills what does not fit to slot (e + 1) % D; one ring for all lanes; the
+ * capacity bound, the lost entries and counters[4] unchanged -- and a released
+ * txn is read from the pool by its src with table bytes and operation words,
+ * as in dv_tpcc_closed_loop_backoff.  n_lanes == 1 is
+ * dv_tpcc_closed_loop_backoff; D = 1 is the plain TPC-C lanes loop bit for
+ * bit.  The attachment records what it is for and its lane count: the TPC-C
+ * lanes loop takes a ring attached through this entry with its own n_lanes
+ * and no other, and dv_tpcc_epoch_run_closed_loop refuses one attached here
+ * with n_lanes > 1 (DV_ERR_STATE).  Refused at attach time: what
+ * dv_closed_loop_backoff_lanes refuses, with the same codes, and a context
+ * that is not DV_TPCC (DV_ERR_ARG).  Detaching the tracker detaches the
+ * back-off; NULL detaches. */
+int dv_tpcc_closed_loop_backoff_lanes(dv_ctx *ctx, const dv_loop_backoff *bo, uint32_t n_lanes);
 
 /* TPC-C epochs over decision lanes (dv_open_lane on a DV_TPCC context), as
  * dv_epoch_run_device_lanes: epoch k decided on lanes[k % n_lanes], executions

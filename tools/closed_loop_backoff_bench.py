@@ -24,8 +24,10 @@ epochs later; `--warmup` and `--epochs` are rounded up to multiples of 2 L
 (dv_tpcc_epoch_run_closed_loop under dv_tpcc_closed_loop_backoff,
 dvcc.TpccLoopBackoff) with bench.py's config-E parameters: `--tpcc-wh`
 warehouses (32), `--cc` (WAIT_DIE), 65,536 txns per epoch unless `--n-txn`
-says otherwise, a pool of two epochs' txns.  One context: TPC-C has no loop
-over decision lanes."""
+says otherwise, a pool of two epochs' txns.  With `--lanes L` it is the TPC-C
+loop over L decision lanes (dv_tpcc_epoch_run_closed_loop_lanes under
+dv_tpcc_closed_loop_backoff_lanes), the legs and the rounding as for the YCSB
+lanes loop."""
 import argparse
 import json
 import os
@@ -55,8 +57,6 @@ def main():
     a = ap.parse_args()
     nl = max(1, a.lanes)
     n_txn = a.n_txn if a.n_txn else (65_536 if a.tpcc else 1_048_576)
-    if a.tpcc and nl > 1:
-        ap.error("--tpcc: one context (TPC-C has no closed loop over decision lanes)")
     if nl > 1:
         a.warmup, a.epochs = (-(-v // (2 * nl)) * 2 * nl for v in (a.warmup, a.epochs))
     if a.tpcc:  # (both set-ups: the pool uploaded before the engine's stream is made current)
@@ -68,8 +68,8 @@ def main():
         torch.cuda.set_stream(torch.cuda.Stream())
         eng = T.TpccEngine(a.cc, tp, n_txn, seed=1)
         eng.set_stream(torch.cuda.current_stream().cuda_stream)
-        ring, what = T.TpccLoopBackoff, {"warehouses": a.tpcc_wh, "cc": a.cc, "pool_txns": pool.n_txn,
-                                         "max_txn_acc": int(dpool.max_txn_acc)}
+        ring = lambda trk, D: T.TpccLoopBackoff(trk, D, lanes=nl)  # noqa: E731
+        what = {"warehouses": a.tpcc_wh, "cc": a.cc, "pool_txns": pool.n_txn, "max_txn_acc": int(dpool.max_txn_acc)}
     else:
         gen = dvcc.YCSBQueryGenerator(a.rows, part_cnt=1, req_per_query=10, zipf_theta=0.9, txn_write_perc=1.0,
                                       tup_write_perc=0.5, part_per_txn=1, strict_ppt=1, mpr=-1.0)
@@ -91,6 +91,10 @@ def main():
     bufs = None
 
     def loop(n, cursor, resume):
+        if a.tpcc and nl > 1:
+            return eng.closed_loop_lanes(lanes, dpool, pargs, pb, n_txn, n, cursor=cursor, bufs=bufs,
+                                         d_commits=[d_commit[k % (2 * nl)] for k in range(n)], resume=resume,
+                                         track=trk)
         if a.tpcc:
             return eng.closed_loop(dpool, pargs, pb, n_txn, n, cursor=cursor, bufs=bufs, d_commits=d_commit,
                                    resume=resume, track=trk)
