@@ -92,10 +92,13 @@ def structural_constants():
     landed accesses), kOwnerTile (the owner split's tile of home accesses:
     dvcc_internal.h's kTile, the radix kernels'), kIlTxns / kIlOwn
     (k_il_move_tb's tile of txns and its LDS index), kMaxPos (the longest txn)
-    and kRouteBlocks, from csrc/."""
+    and kRouteBlocks, and the row-queue kernels' kPV (consecutive accesses of
+    a thread of k_seg_prepare / k_exec), kRIPT and kRTile (a thread's entries
+    and a workgroup's tile of k_calvin_pass), from csrc/."""
     rounds, internal, prefix = _src("dvcc_rounds.hip"), _src("dvcc_internal.h"), _src("dvcc_prefix.hip")
-    comm = _src("dvcc_comm.hip")
+    comm, kernels, common = _src("dvcc_comm.hip"), _src("dvcc_kernels.hip"), _src("dvcc_common.h")
     assert re.search(r"constexpr\s+uint32_t\s+kXTile\s*=\s*kBlock\s*\*\s*kXIPT\s*;", comm)
+    assert re.search(r"constexpr\s+int\s+kRTile\s*=\s*kBlock\s*\*\s*kRIPT\s*;", common)
     assert re.search(r"constexpr\s+int\s+kTile\s*=\s*kBlock\s*\*\s*kIPT\s*;", internal)
     il = re.search(r"constexpr\s+uint32_t\s+kIlTxns\s*=\s*(\d+)\s*,\s*kIlOwn\s*=\s*(\d+)\s*;", comm)
     max_pos = re.search(r"constexpr\s+uint32_t\s+kMaxPos\s*=\s*1u\s*<<\s*(\d+)\s*;", internal)
@@ -120,6 +123,9 @@ def structural_constants():
         kIlOwn=int(il.group(2)),
         kMaxPos=1 << int(max_pos.group(1)),
         kRouteBlocks=_const(internal, "kRouteBlocks"),
+        kPV=_const(kernels, "kPV"),
+        kRIPT=_const(common, "kRIPT"),
+        kRTile=_const(internal, "kBlock") * _const(common, "kRIPT"),
     )
 
 
