@@ -757,6 +757,20 @@ void launch_rsp_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in
                      const ReplyWs &ws);
 void launch_rsp_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
                      const ReplyWs &ws);
+// the sequencer's batch out (dv_wire_sequence_device) over nb client mbufs: the
+// plan leaves the result record in ws.sres, the emit writes nothing where the
+// plan refused the capacities
+void launch_seq_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in &in, const dv_wire_seq_out &out,
+                     uint32_t nb, const WireSeqWs &ws);
+void launch_seq_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in &in, const dv_wire_seq_out &out,
+                     uint32_t nb, const WireSeqWs &ws);
+// the sequencer's acks in (dv_wire_sequence_acks_device): the plan leaves the
+// call's record in ws.ares; the emit packs the replies and changes the wait
+// list only where the plan's status is DV_OK.  n_cap: ack_done_cap
+void launch_ack_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_ack_in &in, const dv_wire_rsp_out &out,
+                     uint32_t n_cap, const AckWs &ws);
+void launch_ack_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_ack_in &in, const dv_wire_rsp_out &out,
+                     uint32_t n_cap, const AckWs &ws);
 
 // ---- prefix-kill epochs (dvcc_prefix.hip)
 // the row-state bitmap (2 bits per row): its 32-bit words for `rows` rows;

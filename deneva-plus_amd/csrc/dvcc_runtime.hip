@@ -4275,6 +4275,64 @@ int dv_wire_respond_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wire_rsp_
     return res->status;
 }
 
+int dv_wire_sequence_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wire_seq_in *in, const dv_wire_seq_out *out,
+                            dv_wire_seq_result *res) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !in || !out || !res || !in->buf || !in->off) return DV_ERR_ARG;
+    if (!out->out || !out->batch_off || !out->dest_first || !out->wait_client || !out->wait_startts || !out->wait_acks)
+        return DV_ERR_ARG;
+    // YCSB under CALVIN; a txn's participants are one 64-bit mask
+    if (cfg->workload != DV_YCSB || cfg->calvin != 1 || !cfg->part_cnt || !cfg->node_cnt ||
+        cfg->node_cnt > DV_WIRE_SEQ_NODE_MAX || cfg->node_id >= cfg->node_cnt)
+        return DV_ERR_ARG;
+    if (in->batch_id == ~0ull || !in->max_txn || in->max_txn > kSeqMaxTxn || in->first_batch > in->n_batches)
+        return DV_ERR_ARG;
+    if (in->n_dest < cfg->node_cnt || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;  // (written in whole dwords)
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // a taken mbuf holds a txn at least: a stopper lies among the first max_txn + 1
+    const uint32_t nb = std::min(in->n_batches - in->first_batch, in->max_txn + 1);
+    WireSeqWs ws;
+    const uint32_t nodes = cfg->node_cnt, max_txn = in->max_txn;
+    int r = wire_words(c, nb, &ws, [&](void *base, uint32_t n, WireSeqWs &w) {
+        return wire_seq_ws_layout(base, n, nodes, max_txn, w);
+    });
+    if (r) return r;
+    launch_seq_plan(c->stream, *cfg, *in, *out, nb, ws);
+    r = wire_record_then_emit(c, ws.sres, sizeof(*res), [&] { launch_seq_emit(c->stream, *cfg, *in, *out, nb, ws); });
+    if (r) return r;
+    std::memcpy(res, c->wire_h, sizeof(*res));
+    return res->status;
+}
+
+int dv_wire_sequence_acks_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in,
+                                 const dv_wire_rsp_out *out, dv_wire_seq_ack_result *res) {
+    KProfScope kps_(c);
+    if (!c || !cfg || !in || !out || !res || !in->buf || !in->off || !out->out || !out->batch_off) return DV_ERR_ARG;
+    if (in->n_txn && (!in->wait_client || !in->wait_startts || !in->wait_acks)) return DV_ERR_ARG;
+    if (cfg->workload != DV_YCSB || cfg->calvin != 1 || !cfg->part_cnt || !cfg->node_cnt ||
+        cfg->node_cnt > DV_WIRE_SEQ_NODE_MAX || cfg->node_id >= cfg->node_cnt)
+        return DV_ERR_ARG;
+    if (in->batch_id == ~0ull || !in->n_dest || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
+    if (in->n_batches > (1u << 26)) return DV_ERR_ARG;  // (a stream position, 64 to an mbuf, in 32 bits)
+    if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;  // (written in whole dwords)
+    if (c->phase != 0) return DV_ERR_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    AckWs ws;
+    const uint32_t n_cap = ack_done_cap(in->n_batches, in->n_txn);
+    int r = scratch_reserve(c, &c->reply_bc, &c->reply_bc_cap,
+                            ack_ws_layout(nullptr, in->n_batches, in->n_txn, in->n_dest, ws));
+    if (!r) r = wire_host_ready(c);
+    if (r) return r;
+    ack_ws_layout(c->reply_bc, in->n_batches, in->n_txn, in->n_dest, ws);
+    launch_ack_plan(c->stream, *cfg, *in, *out, n_cap, ws);
+    r = wire_record_then_emit(c, ws.ares, sizeof(*res), [&] { launch_ack_emit(c->stream, *cfg, *in, *out, n_cap, ws); });
+    if (r) return r;
+    std::memcpy(res, c->wire_h, sizeof(*res));
+    return res->status;
+}
+
 int dv_epoch_reads_tb_only(const dv_ctx *c, uint32_t n_txn) {
     if (!c) return DV_ERR_ARG;
     static const uint32_t word = 0;  // (tb_epoch looks at which arrays are given, never through them)

@@ -1287,28 +1287,36 @@ static_assert(kBlock == DV_WIRE_DEST_MAX && kBlock == kReplyTile, "a thread per 
 // ack's rc -- and kPer of them to a full mbuf.
 struct RspClient {
     static constexpr uint32_t kDw = 21, kType = DV_WIRE_CL_RSP;
-    static constexpr bool kCalvin = false;
+    static constexpr bool kCalvin = false, kSeq = false;
 };
 struct RspCalvin {
     static constexpr uint32_t kDw = 22, kType = DV_WIRE_CALVIN_ACK;
-    static constexpr bool kCalvin = true;
+    static constexpr bool kCalvin = true, kSeq = false;
+};
+// a CALVIN sequencer's CL_RSP (dv_wire_sequence_acks_device): the CALVIN build's header, batch_id UINT64_MAX,
+// then client_startts; the txn id is the sequencer's own, node_id + node_cnt * txn
+struct RspSeq {
+    static constexpr uint32_t kDw = 23, kType = DV_WIRE_CL_RSP;
+    static constexpr bool kCalvin = false, kSeq = true;
 };
 template <class R>
 constexpr uint32_t rsp_per() {
     return (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / (R::kDw * 4);
 }
-static_assert(rsp_per<RspClient>() == 48 && rsp_per<RspCalvin>() == 46, "replies of a full mbuf");
+static_assert(rsp_per<RspClient>() == 48 && rsp_per<RspCalvin>() == 46 && rsp_per<RspSeq>() == 44,
+              "replies of a full mbuf");
 
 // which entries of the call are answered, and by which txn's fields
 struct RspSel {
     uint32_t n, n_src_txn;
     const uint8_t *commit;
     const uint32_t *src, *rnode;
+    const uint32_t *n_dev;  // or NULL: the entries in use, where only the device knows them (at most n)
 };
 
 __device__ __forceinline__ bool rsp_answered(const RspSel &s, uint32_t i, uint32_t &txn) {
     txn = i;
-    if (i >= s.n) return false;
+    if (i >= s.n || (s.n_dev && i >= *s.n_dev)) return false;
     if (s.src) {
         txn = s.src[i];
         return true;
@@ -1323,6 +1331,7 @@ __device__ __forceinline__ uint32_t rsp_dword(uint32_t f, uint64_t txn_id, uint6
     constexpr uint32_t t0 = R::kCalvin ? 3 : R::kDw - 2;
     if (f == 0) return R::kType;
     if (f <= 2) return (uint32_t)(txn_id >> (32 * (f - 1)));
+    if (R::kSeq && f <= 4) return 0xFFFFFFFFu;
     if (f == t0 || f == t0 + 1) return (uint32_t)(tail >> (32 * (f - t0)));
     return 0;
 }
@@ -1359,7 +1368,8 @@ __device__ __forceinline__ void rsp_emit(const RspSel &sel, uint32_t nt, uint32_
         const uint32_t r = ws.cnt[(uint64_t)d * nt + blockIdx.x] + in_tile;
         const uint32_t j = r / per, mb = ws.dmb[d] + j;
         const uint64_t pos = 3ull * ((uint64_t)mb + 1) + (uint64_t)R::kDw * ((uint64_t)ws.dmsg[d] + r);
-        const uint64_t id = txn_id[txn], tail = R::kCalvin ? batch_id : cst[txn];
+        // (RspSeq: batch_id carries node_cnt)
+        const uint64_t id = R::kSeq ? node_id + batch_id * txn : txn_id[txn], tail = R::kCalvin ? batch_id : cst[txn];
         if (r == j * per) {  // the mbuf's first message: its header and offset
             const uint32_t left = ws.tot[d] - r;
             out[pos - 3] = d;
@@ -1454,7 +1464,7 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit_calvin(RspSel sel, uint32_t
 }
 
 static RspSel rsp_sel(const dv_wire_rsp_in &in) {
-    return RspSel{in.n, in.n_src_txn, in.commit, in.src, in.return_node};
+    return RspSel{in.n, in.n_src_txn, in.commit, in.src, in.return_node, nullptr};
 }
 
 void launch_rsp_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in &in, const dv_wire_rsp_out &out,
@@ -1481,6 +1491,559 @@ void launch_rsp_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_rsp_in
     else
         DV_LAUNCH(k_rsp_emit, nt, kBlock, 0, s, rsp_sel(in), nt, cfg.node_id, in.txn_id, in.client_startts, ws, out32,
                   out.batch_off);
+}
+
+// ---- the CALVIN sequencer's batch out (dv_wire_sequence_device): what
+// dv_wire_sequence (csrc/wire.cpp) writes.  Check, scan and plan as the
+// ingests' -- a wave per client mbuf over a third dialect, Seq: a CALVIN
+// build's 84-byte header on a client's CL_QRY, no RDONE -- then the new part,
+// the cut.  A destination's messages (and its RDONE) are a list; an entry's
+// bytes in front of it, S, come from per-(destination, mbuf) counts scanned per
+// destination (k_seq_dscan) and a wave's own prefix (k_seq_list).  next(i), the
+// first entry that no longer fits an mbuf opened at i, is a search on S, and
+// the mbuf starts are the entries reachable from 0 along next.  They are
+// resolved by pointer jumping inside tiles of kSeqTile entries in LDS
+// (k_seq_tiles: from every entry, where the walk leaves the tile and the mbufs
+// it opens on the way), one thread per destination chaining the tiles
+// (k_seq_chain: where the walk enters each tile), and the tiles marking their
+// starts from that entry by the jump levels (k_seq_marks), which also places
+// every entry in out and writes the mbuf headers, the offsets and the RDONEs.
+// The second plan (k_seq_plan2) decides bytes and mbufs against the capacities
+// before any of that is written.  The emit (k_seq_emit) stages a taken mbuf
+// again and copies each message once per participant, consecutive lanes on
+// consecutive dwords of a message: every size is a multiple of 4 and out is
+// 4-byte aligned, so out is written in whole dwords, each once.
+namespace {
+
+struct Seq {
+    static constexpr uint32_t kHdr = 84, kFixed = 100, kStride = kWireMaxMsg;
+    static constexpr bool kRdone = false;
+};
+constexpr uint32_t kSeqRoom = kWireMsgMax - DV_WIRE_HDR;  // message bytes of an mbuf
+constexpr uint32_t kSeqHdrDw = Seq::kHdr / 4;
+
+// lane d: where destination d's list starts (every lane of the wave calls)
+__device__ __forceinline__ uint32_t seq_list_base(const uint32_t *__restrict__ dtot, uint32_t nodes, uint32_t lane) {
+    const uint32_t v = lane < nodes ? dtot[lane] + 2u : 0u;
+    return wave_incl_sum(v, lane) - v;
+}
+
+// s[i]: the bytes in front of entry r0 + i of a destination's list (tot
+// messages of totb bytes, then the RDONE; behind the list's end: nothing fits),
+// for a tile and the reach behind it.  Every thread of the block; a barrier.
+__device__ __forceinline__ void seq_tile_sums(const uint32_t *__restrict__ lS, uint32_t tot, uint32_t totb, uint32_t r0,
+                                              uint32_t *s) {
+    for (uint32_t i = threadIdx.x; i < kSeqTile + kSeqReach; i += kBlock) {
+        const uint32_t r = r0 + i;
+        s[i] = r < tot ? lS[r] : (r == tot ? totb : (r == tot + 1 ? totb + Seq::kHdr : 0xFFFFFFFFu));
+    }
+    __syncthreads();
+}
+
+// the first entry that does not fit an mbuf opened at entry i (both tile-local): a message is 108 bytes at
+// least and the RDONE 84, so it lies fewer than kSeqReach entries on
+__device__ __forceinline__ uint32_t seq_next(const uint32_t *s, uint32_t i) {
+    const uint32_t target = s[i] + kSeqRoom;
+    uint32_t k = 0;
+#pragma unroll
+    for (uint32_t w = kSeqReach / 2; w > 0; w >>= 1)
+        if (s[i + k + w] <= target) k += w;
+    return i + k;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kBlock) void k_seq_check(dv_wire_cfg cfg, uint32_t n_dest,
+                                                      const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                      const uint64_t *__restrict__ off, uint32_t first, uint32_t nb,
+                                                      WireSeqWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ YcsbTables s_t;
+    __shared__ uint32_t s_pm[kWireWave][64][2];  // message m's participants
+    __shared__ uint16_t s_sz[kWireWave][64];     // its bytes
+    s_pm[threadIdx.x >> 6][threadIdx.x & 63][0] = 0;
+    s_pm[threadIdx.x >> 6][threadIdx.x & 63][1] = 0;
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane, wave = w.wave;
+    const bool parse = w.live && !w.bad;
+    uint32_t count = 0, tot_rq = 0;
+    Msg my{};
+    bool bad = ycsb_batch_bad<Seq>(w, cfg, 0, s_t, count, my, tot_rq);
+    if (parse && !bad) {  // ISCLIENTN(src); a txn has a request at least
+        const uint32_t src = st.u32(4);
+        bad = src < cfg.node_cnt || src >= n_dest;
+    }
+    bad = bad || __any(parse && lane < count && my.n == 0);
+    if (parse && !bad)  // YCSBQuery::participants: GET_NODE_ID(key_to_part(key))
+        for (uint32_t r = lane; r < tot_rq; r += 64) {
+            const uint32_t m = last_le64(s_t.rq[wave], r);
+            const uint64_t key = st.u64(s_t.p2[wave][m] + 8u + (r - s_t.rq[wave][m]) * kReqBytes + 8u);
+            const uint32_t node = (uint32_t)((key % cfg.part_cnt) % cfg.node_cnt);
+            atomicOr(&s_pm[wave][m][node >> 5], 1u << (node & 31u));
+        }
+    const uint32_t size = parse && !bad && lane < count ? my.bo + 8u + my.n * kReqBytes - my.off : 0u;
+    s_sz[wave][lane] = (uint16_t)size;
+    __syncthreads();
+    const uint64_t mask = parse && !bad && lane < count ? ((uint64_t)s_pm[wave][lane][1] << 32) | s_pm[wave][lane][0] : 0;
+    const uint32_t sends = __shfl(wave_incl_sum((uint32_t)__popcll(mask), lane), 63, 64);
+    if (!w.live) return;
+    keep_batch<Seq>(ws, w, bad, count, my.off, count, sends, count);  // (bm: the mbuf's messages)
+    if (!bad && lane < count) {
+        ws.mmask[(uint64_t)w.b * Seq::kStride + lane] = mask;
+        ws.msz[(uint64_t)w.b * Seq::kStride + lane] = (uint16_t)size;
+    }
+    if (lane < cfg.node_cnt) {  // destination `lane`: its messages and bytes of this mbuf
+        uint32_t c = 0, by = 0;
+        for (uint32_t m = 0; !bad && m < count; m++)
+            if (s_pm[wave][m][lane >> 5] >> (lane & 31u) & 1u) c++, by += s_sz[wave][m];
+        ws.dcnt[(uint64_t)lane * nb + w.b] = c;
+        ws.dbyt[(uint64_t)lane * nb + w.b] = by;
+    }
+}
+
+// One workgroup: k_wire_plan's cut over the txns alone
+__global__ __launch_bounds__(kBlock) void k_seq_plan(WireSeqWs ws, uint32_t first, uint32_t nb, uint32_t n_batches,
+                                                     uint32_t nc, uint32_t max_txn) {
+    __shared__ uint32_t lds4[4], s_chunk, s_cut;
+    if (threadIdx.x == 0) {
+        s_chunk = nc;
+        s_cut = nb;
+    }
+    const uint32_t tot_t = block_chunk_scan256(ws.ct, nc, lds4);
+    const uint32_t tot_a = block_chunk_scan256(ws.ca, nc, lds4);
+    __syncthreads();
+    const uint32_t cut = first_overflow(ws, nb, nc, tot_t, tot_a, max_txn, ~0ull, &s_chunk, &s_cut);
+    const uint32_t fb = ws.first[0];
+    const uint32_t k = fb < cut ? fb : cut;
+    if (threadIdx.x != 0) return;
+    WireSeqPlan p{};
+    p.taken = k;
+    p.n_txn = sum_below(ws.ct, ws.bt, k, nb, tot_t);
+    p.n_msgs = sum_below(ws.ca, ws.ba, k, nb, tot_a);
+    p.status = DV_OK;
+    if (fb < nb && fb <= cut) p.status = DV_ERR_ARG;
+    else if (cut < nb) p.status = cut ? DV_WIRE_MORE : DV_ERR_ARG;
+    else if (first + nb < n_batches) p.status = DV_WIRE_MORE;
+    *ws.plan = p;
+}
+
+// destination blockIdx.x: its counts per taken mbuf become those in front of the mbuf
+__global__ __launch_bounds__(kBlock) void k_seq_dscan(WireSeqWs ws, uint32_t nb) {
+    __shared__ uint32_t lds4[4];
+    const uint32_t taken = ws.plan->taken;
+    const uint32_t c = block_chunk_scan256(ws.dcnt + (uint64_t)blockIdx.x * nb, taken, lds4);
+    const uint32_t by = block_chunk_scan256(ws.dbyt + (uint64_t)blockIdx.x * nb, taken, lds4);
+    if (threadIdx.x == 0) {
+        ws.dtot[blockIdx.x] = c;
+        ws.dtotb[blockIdx.x] = by;
+    }
+}
+
+// a wave per taken mbuf: every (message, participant) its list entry's S
+__global__ __launch_bounds__(kBlock) void k_seq_list(WireSeqWs ws, uint32_t nb, uint32_t nodes) {
+    const uint32_t lane = threadIdx.x & 63, b = blockIdx.x * kWireWave + (threadIdx.x >> 6);
+    if (b >= ws.plan->taken) return;  // (the whole wave)
+    const uint32_t lb = seq_list_base(ws.dtot, nodes, lane);
+    const uint32_t count = ws.bm[b];
+    const uint64_t mask = lane < count ? ws.mmask[(uint64_t)b * Seq::kStride + lane] : 0;
+    const uint32_t size = lane < count ? ws.msz[(uint64_t)b * Seq::kStride + lane] : 0u;
+    for (uint32_t d = 0; d < nodes; d++) {
+        const bool has = mask >> d & 1u;
+        const uint64_t bal = __ballot(has);
+        if (!bal) continue;
+        const uint32_t mine = has ? size : 0u, pre = wave_incl_sum(mine, lane) - mine;
+        const uint32_t e = __shfl(lb, (int)d, 64) + ws.dcnt[(uint64_t)d * nb + b] + mask_rank(bal);
+        if (has) ws.lS[e] = ws.dbyt[(uint64_t)d * nb + b] + pre;
+    }
+}
+
+// tile blockIdx.x of destination blockIdx.y: from every entry, the walk along next inside the tile
+__global__ __launch_bounds__(kBlock) void k_seq_tiles(WireSeqWs ws, uint32_t nodes) {
+    __shared__ uint32_t s_S[kSeqTile + kSeqReach];
+    __shared__ uint16_t s_p[kSeqTile], s_c[kSeqTile];
+    static_assert(kSeqTile == kBlock, "a thread per entry");
+    const uint32_t d = blockIdx.y, r0 = blockIdx.x * kSeqTile, tot = ws.dtot[d], L = tot + 1, i = threadIdx.x;
+    if (r0 >= L) return;  // (the whole block)
+    const uint32_t lb = __shfl(seq_list_base(ws.dtot, nodes, i & 63), (int)d, 64);
+    seq_tile_sums(ws.lS + lb, tot, ws.dtotb[d], r0, s_S);
+    const bool valid = r0 + i < L;
+    uint32_t p = valid ? seq_next(s_S, i) : kSeqTile, c = valid ? 1u : 0u;  // (behind the list: out at once, no mbuf)
+    s_p[i] = (uint16_t)p;
+    s_c[i] = (uint16_t)c;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t round = 0; round < 8; round++) {  // (2^8 = kSeqTile steps at most)
+        uint32_t np = p, ac = 0;
+        if (p < kSeqTile) {
+            np = s_p[p];
+            ac = s_c[p];
+        }
+        __syncthreads();
+        p = np;
+        c += ac;
+        s_p[i] = (uint16_t)p;
+        s_c[i] = (uint16_t)c;
+        __syncthreads();
+    }
+    if (valid) ws.ljmp[lb + r0 + i] = c << 8 | (p - kSeqTile);
+}
+
+// destination blockIdx.x, one thread: the walk from entry 0 from tile to tile
+__global__ __launch_bounds__(64) void k_seq_chain(WireSeqWs ws, uint32_t nodes, uint32_t ntile) {
+    const uint32_t d = blockIdx.x, lane = threadIdx.x;
+    const uint32_t lb = __shfl(seq_list_base(ws.dtot, nodes, lane), (int)d, 64), L = ws.dtot[d] + 1;
+    if (lane != 0) return;
+    uint32_t x = 0, mbs = 0, t_next = 0;
+    while (x < L) {
+        const uint32_t t = x / kSeqTile, j = ws.ljmp[lb + x];
+        ws.tent[(uint64_t)d * ntile + t] = x % kSeqTile;
+        ws.tmb[(uint64_t)d * ntile + t] = mbs;
+        mbs += j >> 8;
+        x = (t + 1) * kSeqTile + (j & 255u);
+        t_next = t + 1;
+    }
+    // (the last mbuf may reach over the list's last tile: the walk never enters it, no entry of it is a start)
+    for (uint32_t t = t_next; t * kSeqTile < L; t++) {
+        ws.tent[(uint64_t)d * ntile + t] = kNoBatch;
+        ws.tmb[(uint64_t)d * ntile + t] = mbs;
+    }
+    ws.dmb[d] = mbs;
+}
+
+// one thread: the destinations' first mbufs and bytes, and the call's fate -- before any output is written
+__global__ __launch_bounds__(64) void k_seq_plan2(WireSeqWs ws, uint32_t nodes, uint32_t first, uint64_t cap,
+                                                  uint32_t max_batches) {
+    if (threadIdx.x != 0) return;
+    uint32_t mb = 0;
+    uint64_t by = 0;
+    for (uint32_t d = 0; d < nodes; d++) {
+        ws.dMB[d] = mb;
+        ws.dDB[d] = by;
+        mb += ws.dmb[d];
+        by += (uint64_t)ws.dtotb[d] + Seq::kHdr + (uint64_t)DV_WIRE_HDR * ws.dmb[d];
+    }
+    const WireSeqPlan p = *ws.plan;
+    const bool refused = by > cap || mb > max_batches;
+    ws.plan->refused = refused ? 1u : 0u;
+    dv_wire_seq_result r;
+    r.status = refused ? DV_ERR_ARG : p.status;
+    r.n_taken = first + p.taken;
+    r.n_txn = p.n_txn;
+    r.n_out = mb;
+    r.n_msgs = p.n_msgs;
+    r.n_bytes = by;
+    *ws.sres = r;
+}
+
+// the tiles again: the starts reachable from where the walk enters the tile,
+// every entry's byte in out, the mbufs' headers and offsets, the RDONE
+__global__ __launch_bounds__(kBlock) void k_seq_marks(WireSeqWs ws, uint32_t nodes, uint32_t ntile, uint32_t node_id,
+                                                      uint64_t batch_id, uint32_t *__restrict__ out,
+                                                      uint64_t *__restrict__ batch_off,
+                                                      uint32_t *__restrict__ dest_first) {
+    __shared__ uint32_t s_S[kSeqTile + kSeqReach], s_mark[kSeqTile], lds4[4];
+    __shared__ uint16_t s_lv[8][kSeqTile];  // level k: 2^k steps along next, kSeqTile: out of the tile
+    if (ws.plan->refused) return;
+    const uint32_t d = blockIdx.y, r0 = blockIdx.x * kSeqTile, tot = ws.dtot[d], L = tot + 1, i = threadIdx.x;
+    if (r0 >= L) return;  // (the whole block)
+    const uint32_t lb = __shfl(seq_list_base(ws.dtot, nodes, i & 63), (int)d, 64);
+    seq_tile_sums(ws.lS + lb, tot, ws.dtotb[d], r0, s_S);
+    const uint32_t r = r0 + i;
+    const bool valid = r < L;
+    const uint32_t nxt = valid ? seq_next(s_S, i) : kSeqTile;
+    s_lv[0][i] = (uint16_t)(nxt < kSeqTile ? nxt : kSeqTile);
+    s_mark[i] = i == ws.tent[(uint64_t)d * ntile + blockIdx.x] ? 1u : 0u;
+    __syncthreads();
+    for (uint32_t k = 1; k < 8; k++) {
+        const uint32_t v = s_lv[k - 1][i];
+        s_lv[k][i] = v < kSeqTile ? s_lv[k - 1][v] : (uint16_t)kSeqTile;
+        __syncthreads();
+    }
+    // (a mark set and followed inside one level is a step along next all the same: only entries of the walk are marked)
+    for (int k = 7; k >= 0; k--) {
+        const uint32_t v = s_lv[k][i];
+        if (s_mark[i] && v < kSeqTile) s_mark[v] = 1u;
+        __syncthreads();
+    }
+    const bool start = valid && s_mark[i] != 0;  // (the list's end may be marked: no entry)
+    const uint32_t before = block_excl_scan256(start ? 1u : 0u, lds4, nullptr);
+    if (valid) {
+        const uint32_t j = ws.tmb[(uint64_t)d * ntile + blockIdx.x] + before + (start ? 1u : 0u) - 1u;  // its mbuf
+        const uint64_t pos = ws.dDB[d] + (uint64_t)DV_WIRE_HDR * (j + 1) + s_S[i], q = pos >> 2;
+        ws.lpos[lb + r] = pos;
+        if (start && j < ws.dmb[d]) {  // (always: the chain counted the same starts)
+            out[q - 3] = d;
+            out[q - 2] = node_id;
+            out[q - 1] = nxt - i;
+            batch_off[ws.dMB[d] + j] = pos - DV_WIRE_HDR;
+        }
+        if (r == tot && pos + Seq::kHdr <= ws.sres->n_bytes) {  // the RDONE: the header alone (the bound: always)
+            out[q] = DV_WIRE_RDONE;
+            out[q + 1] = out[q + 2] = 0xFFFFFFFFu;
+            out[q + 3] = (uint32_t)batch_id;
+            out[q + 4] = (uint32_t)(batch_id >> 32);
+            for (uint32_t f = 5; f < kSeqHdrDw; f++) out[q + f] = 0;
+        }
+    }
+    if (blockIdx.x == 0 && i == 0) {
+        dest_first[d] = ws.dMB[d];
+        if (d == 0) {
+            dest_first[nodes] = ws.sres->n_out;
+            batch_off[ws.sres->n_out] = ws.sres->n_bytes;
+        }
+    }
+}
+
+// the taken mbufs, a wave each: the wait list, and every message once per participant
+__global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
+                                                     const uint64_t *__restrict__ off, uint32_t first, uint32_t nb,
+                                                     uint64_t batch_id, WireSeqWs ws, uint32_t *__restrict__ out,
+                                                     uint32_t *__restrict__ wait_client,
+                                                     uint64_t *__restrict__ wait_startts,
+                                                     uint32_t *__restrict__ wait_acks) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    const uint32_t taken = ws.plan->taken;
+    if (ws.plan->refused || blockIdx.x * kWireWave >= taken) return;
+    const WaveBatch w = stage_taken_batch(s_img, buf, off, first, taken);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane;
+    const uint32_t lb = seq_list_base(ws.dtot, cfg.node_cnt, lane);
+    if (!w.live) return;
+    const uint32_t b = w.b, count = ws.bm[b], t0 = ws.ct[b / kWireChunk] + ws.bt[b];
+    const uint64_t end = ws.sres->n_bytes >> 2;  // (no store at or past it, whatever the words above hold)
+    uint64_t mask = 0;
+    uint32_t size = 0, mo = 0;
+    if (lane < count) {
+        mo = ws.moff[(uint64_t)b * Seq::kStride + lane];
+        mask = ws.mmask[(uint64_t)b * Seq::kStride + lane];
+        size = ws.msz[(uint64_t)b * Seq::kStride + lane];
+        wait_client[t0 + lane] = st.u32(4);
+        wait_startts[t0 + lane] = st.u64(mo + Seq::kHdr);
+        wait_acks[t0 + lane] = (uint32_t)__popcll(mask);
+    }
+    for (uint32_t d = 0; d < cfg.node_cnt; d++) {
+        const bool has = mask >> d & 1u;
+        uint64_t bal = __ballot(has);
+        if (!bal) continue;
+        const uint32_t e = __shfl(lb, (int)d, 64) + ws.dcnt[(uint64_t)d * nb + b] + mask_rank(bal);
+        const uint64_t pos = has ? ws.lpos[e] : 0;
+        while (bal) {  // the messages to d, one after the other: consecutive lanes, consecutive dwords
+            const uint32_t m = (uint32_t)__builtin_ctzll(bal);
+            bal &= bal - 1;
+            const uint64_t q = shfl_u64(pos, m) >> 2;
+            const uint32_t o = __shfl(mo, (int)m, 64), ndw = __shfl(size, (int)m, 64) >> 2;
+            const uint64_t id = worker_txn_id(cfg, t0 + m);
+            for (uint32_t f = lane; f < ndw && q + f < end; f += 64) {
+                uint32_t v = 0;  // mq_time, the latencies
+                if (f == 0) v = DV_WIRE_CL_QRY;
+                else if (f <= 2) v = (uint32_t)(id >> (32 * (f - 1)));
+                else if (f <= 4) v = (uint32_t)(batch_id >> (32 * (f - 3)));
+                else if (f >= kSeqHdrDw) v = st.u32(o + 4 * f);
+                out[q + f] = v;
+            }
+        }
+    }
+}
+
+void launch_seq_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in &in, const dv_wire_seq_out &out,
+                     uint32_t nb, const WireSeqWs &ws) {
+    const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk, nodes = cfg.node_cnt, nbn = nb ? nb : 1;
+    const uint32_t ntile = wire_seq_tiles(nbn, in.max_txn), grid = (nb + kWireWave - 1) / kWireWave;
+    (void)hipMemsetAsync(ws.first, 0xFF, 2 * sizeof(uint32_t), s);  // kNoBatch
+    if (nb) {
+        DV_LAUNCH(k_seq_check, grid, kBlock, 0, s, cfg, in.n_dest, in.buf, in.buf_len, in.off, in.first_batch, nb, ws);
+        DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
+    }
+    DV_LAUNCH(k_seq_plan, 1, kBlock, 0, s, ws, in.first_batch, nb, in.n_batches, nc, in.max_txn);
+    DV_LAUNCH(k_seq_dscan, nodes, kBlock, 0, s, ws, nbn);
+    if (nb) DV_LAUNCH(k_seq_list, grid, kBlock, 0, s, ws, nbn, nodes);
+    DV_LAUNCH(k_seq_tiles, dim3(ntile, nodes), kBlock, 0, s, ws, nodes);
+    DV_LAUNCH(k_seq_chain, nodes, 64, 0, s, ws, nodes, ntile);
+    DV_LAUNCH(k_seq_plan2, 1, 64, 0, s, ws, nodes, in.first_batch, out.cap, out.max_batches);
+}
+
+void launch_seq_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in &in, const dv_wire_seq_out &out,
+                     uint32_t nb, const WireSeqWs &ws) {
+    const uint32_t nodes = cfg.node_cnt, nbn = nb ? nb : 1, ntile = wire_seq_tiles(nbn, in.max_txn);
+    uint32_t *out32 = reinterpret_cast<uint32_t *>(out.out);
+    DV_LAUNCH(k_seq_marks, dim3(ntile, nodes), kBlock, 0, s, ws, nodes, ntile, cfg.node_id, in.batch_id, out32,
+              out.batch_off, out.dest_first);
+    if (nb)
+        DV_LAUNCH(k_seq_emit, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, in.buf, in.off, in.first_batch, nbn,
+                  in.batch_id, ws, out32, out.wait_client, out.wait_startts, out.wait_acks);
+}
+
+// ---- the sequencer's acks in (dv_wire_sequence_acks_device): what
+// dv_wire_sequence_acks (csrc/wire.cpp) does.  A wave per ack mbuf, staged as
+// the ingests stage theirs, three times over the same bytes: the form, the
+// per-txn ack counts and last positions (k_ack_count: vector atomics on scratch
+// words, never on the wait list), the checks against the wait list and the
+// completing acks per mbuf (k_ack_mark<false>), and, behind a scan, the
+// completed txns in completing position order (k_ack_mark<true>).  That list
+// goes through the reply packer as it is -- its count, scan, plan and emit over
+// a third reply dialect, RspSeq -- and the wait list changes only behind the
+// plan (k_ack_apply), where the whole call is known to stand.
+namespace {
+constexpr uint32_t kAckBytes = 88, kAckPer = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / kAckBytes;
+static_assert(kAckPer == 46 && kAckPer <= 64, "a lane per ack");
+
+// the wave's ack mbuf: bad where its form is wrong; lane m < count: message m,
+// `mine` where it is an ack of batch_id for txn k of this sequencer
+__device__ __forceinline__ bool ack_mbuf(const WaveBatch &w, const dv_wire_cfg &cfg, uint64_t batch_id, uint32_t n_txn,
+                                         uint32_t &count, bool &mine, uint32_t &k) {
+    const Stage &st = w.st;
+    mine = false;
+    count = k = 0;
+    if (!w.live || w.bad) return true;
+    count = st.u32(8);
+    if (st.u32(0) != cfg.node_id || st.u32(4) >= cfg.node_cnt || count < 1 || count > kAckPer ||
+        w.len != DV_WIRE_HDR + kAckBytes * count)
+        return true;
+    bool wrong = false;
+    if (w.lane < count) {
+        const uint32_t o = DV_WIRE_HDR + kAckBytes * w.lane;
+        const uint64_t tid = st.u64(o + kCalTxnId), bid = st.u64(o + kCalBatchId);
+        wrong = st.u32(o) != DV_WIRE_CALVIN_ACK || bid == kNoBatchId;
+        if (!wrong && bid == batch_id) {
+            wrong = tid % cfg.node_cnt != cfg.node_id || tid / cfg.node_cnt >= n_txn;
+            mine = !wrong;
+            k = (uint32_t)(tid / cfg.node_cnt);
+        }
+    }
+    return __any(wrong);
+}
+}  // namespace
+
+__global__ __launch_bounds__(kBlock) void k_ack_count(dv_wire_cfg cfg, const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                      const uint64_t *__restrict__ off, uint32_t nb, uint64_t batch_id,
+                                                      uint32_t n_txn, AckWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, 0, nb);
+    uint32_t count, k;
+    bool mine;
+    const bool bad = ack_mbuf(w, cfg, batch_id, n_txn, count, mine, k);
+    if (!w.live) return;
+    if (bad) {
+        if (w.lane == 0) {
+            atomicMin(ws.first, w.b);
+            atomicOr(ws.r.err, 1u);
+        }
+        return;
+    }
+    if (mine) {
+        atomicAdd(&ws.acnt[k], 1u);
+        atomicMax(&ws.alast[k], w.b * 64u + w.lane);  // the stream position: mbuf-major, message-minor
+    }
+    const uint32_t n_mine = (uint32_t)__popcll(__ballot(mine));
+    if (w.lane == 0) {
+        atomicAdd(&ws.counts[0], n_mine);
+        atomicAdd(&ws.counts[1], count - n_mine);
+    }
+}
+
+// LIST false: the txns' counts against the wait list, the completing acks per
+// mbuf; true (behind the scan): the completed txns in position order
+template <bool LIST>
+__global__ __launch_bounds__(kBlock) void k_ack_mark(dv_wire_cfg cfg, const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                     const uint64_t *__restrict__ off, uint32_t nb, uint64_t batch_id,
+                                                     uint32_t n_txn, uint32_t n_dest,
+                                                     const uint32_t *__restrict__ wait_client,
+                                                     const uint32_t *__restrict__ wait_acks, AckWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    if (*ws.r.err) return;  // (a malformed mbuf, or LIST: any refusal -- the call fails whole)
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, 0, nb);
+    uint32_t count, k;
+    bool mine;
+    (void)ack_mbuf(w, cfg, batch_id, n_txn, count, mine, k);
+    if (!w.live) return;
+    bool completing = false;
+    if (mine) {
+        const uint32_t c = ws.acnt[k], wa = wait_acks[k];
+        completing = c == wa && ws.alast[k] == w.b * 64u + w.lane;
+        if (!LIST && (c > wa || (completing && wait_client[k] >= n_dest))) atomicOr(ws.err2, 1u);
+    }
+    const uint64_t bal = __ballot(completing);
+    if (!LIST) {
+        if (w.lane == 0) ws.bt[w.b] = (uint32_t)__popcll(bal);
+    } else if (completing) {
+        ws.done[ws.bt[w.b] + mask_rank(bal)] = k;
+    }
+}
+
+// one workgroup: the completing acks in front of every mbuf, the completed txns
+__global__ __launch_bounds__(kBlock) void k_ack_scan(AckWs ws, uint32_t nb) {
+    __shared__ uint32_t lds4[4];
+    const bool bad = *ws.r.err || *ws.err2;
+    const uint32_t tot = bad ? 0u : block_chunk_scan256(ws.bt, nb, lds4);
+    if (threadIdx.x != 0) return;
+    ws.counts[2] = tot;
+    if (bad) *ws.r.err = 1u;  // (the packer's plan refuses the call: nothing is written)
+}
+
+// behind the packer's plan: the call's record
+__global__ __launch_bounds__(64) void k_ack_final(AckWs ws) {
+    if (threadIdx.x != 0) return;
+    const dv_wire_rsp_result p = *ws.r.res;
+    dv_wire_seq_ack_result r{DV_ERR_ARG, *ws.first, 0, 0, 0, 0, 0};
+    if (!*ws.r.err) {  // (else: malformed, over-acked or a client out of range: no count is reported)
+        r.status = p.status;
+        r.n_acks = ws.counts[0];
+        r.n_skipped = ws.counts[1];
+        r.n_done = ws.counts[2];
+        r.n_batches = p.n_batches;
+        r.n_bytes = p.n_bytes;
+    }
+    *ws.ares = r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_ack_apply(AckWs ws, uint32_t n_txn, uint32_t *__restrict__ wait_acks) {
+    if (ws.r.res->status != DV_OK) return;
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k < n_txn) wait_acks[k] -= ws.acnt[k];
+}
+
+__global__ __launch_bounds__(kBlock) void k_rsp_emit_seq(RspSel sel, uint32_t nt, uint32_t node_id, uint32_t node_cnt,
+                                                         const uint64_t *__restrict__ cst, ReplyWs ws,
+                                                         uint32_t *__restrict__ out, uint64_t *__restrict__ batch_off) {
+    rsp_emit<RspSeq>(sel, nt, node_id, node_cnt, nullptr, cst, ws, out, batch_off);
+}
+
+static RspSel ack_sel(const dv_wire_seq_ack_in &in, const AckWs &ws, uint32_t n_cap) {
+    return RspSel{n_cap, in.n_txn, nullptr, ws.done, in.wait_client, ws.counts + 2};
+}
+
+void launch_ack_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_ack_in &in, const dv_wire_rsp_out &out,
+                     uint32_t n_cap, const AckWs &ws) {
+    const uint32_t nb = in.n_batches, grid = (nb + kWireWave - 1) / kWireWave, nt = reply_tiles(n_cap);
+    (void)hipMemsetAsync(ws.first, 0xFF, sizeof(uint32_t), s);  // DV_WIRE_NO_BATCH
+    (void)hipMemsetAsync(ws.zeroed, 0, ws.zeroed_bytes, s);     // err2, counts, acnt, alast
+    (void)hipMemsetAsync(ws.r.err, 0, sizeof(uint32_t), s);
+    if (nb) {
+        DV_LAUNCH(k_ack_count, grid, kBlock, 0, s, cfg, in.buf, in.buf_len, in.off, nb, in.batch_id, in.n_txn, ws);
+        DV_LAUNCH(k_ack_mark<false>, grid, kBlock, 0, s, cfg, in.buf, in.buf_len, in.off, nb, in.batch_id, in.n_txn,
+                  in.n_dest, in.wait_client, in.wait_acks, ws);
+    }
+    DV_LAUNCH(k_ack_scan, 1, kBlock, 0, s, ws, nb);
+    if (nb)
+        DV_LAUNCH(k_ack_mark<true>, grid, kBlock, 0, s, cfg, in.buf, in.buf_len, in.off, nb, in.batch_id, in.n_txn,
+                  in.n_dest, in.wait_client, in.wait_acks, ws);
+    if (nt) {
+        DV_LAUNCH(k_rsp_count, nt, kBlock, 0, s, ack_sel(in, ws, n_cap), in.n_dest, nt, ws.r);
+        DV_LAUNCH(k_rsp_scan, in.n_dest, kBlock, 0, s, ws.r, nt);
+    }
+    DV_LAUNCH(k_rsp_plan, 1, kBlock, 0, s, ws.r, nt, in.n_dest, rsp_per<RspSeq>(), 4 * RspSeq::kDw, out.cap,
+              out.max_batches, out.batch_off);
+    DV_LAUNCH(k_ack_final, 1, 64, 0, s, ws);
+}
+
+void launch_ack_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_ack_in &in, const dv_wire_rsp_out &out,
+                     uint32_t n_cap, const AckWs &ws) {
+    const uint32_t nt = reply_tiles(n_cap);
+    if (nt)
+        DV_LAUNCH(k_rsp_emit_seq, nt, kBlock, 0, s, ack_sel(in, ws, n_cap), nt, cfg.node_id, cfg.node_cnt, in.wait_startts,
+                  ws.r, reinterpret_cast<uint32_t *>(out.out), out.batch_off);
+    if (in.n_txn) DV_LAUNCH(k_ack_apply, (in.n_txn + kBlock - 1) / kBlock, kBlock, 0, s, ws, in.n_txn, in.wait_acks);
 }
 
 }  // namespace dvcc

@@ -49,6 +49,52 @@ struct WireCalvinWs : WireWs {
     WireCalvinRes *cres;  // (res, as the record it holds here)
 };
 
+// The sequencer (dv_wire_sequence_device): a batch is a client mbuf of at most
+// kWireMaxMsg CL_QRYs (108 bytes each at least), bm its message count, ba the
+// messages it sends (its txns' participants).  A destination's messages and
+// its RDONE are a list; the lists lie back to back, destination d's at lb[d] =
+// sum over d' < d of (dtot[d'] + 2).  The cut search takes kSeqTile list
+// entries per workgroup; a message that no longer fits an mbuf lies fewer than
+// kSeqReach entries behind the mbuf's first.
+constexpr uint32_t kSeqTile = 256;
+constexpr uint32_t kSeqReach = 64;
+constexpr uint32_t kSeqMaxTxn = 1u << 20;  // (a destination's bytes stay in 32 bits)
+constexpr uint32_t kSeqMbufParts = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / 24;  // requests, so participants, of an mbuf
+static_assert((uint64_t)kSeqMaxTxn * (DV_WIRE_MSG_MAX - DV_WIRE_HDR) + 84 + DV_WIRE_MSG_MAX < (1ull << 32),
+              "a destination's bytes and a cut's target in 32 bits");
+struct WireSeqPlan {  // what the first plan leaves for the kernels behind it
+    uint32_t taken, n_txn, n_msgs;
+    int32_t status;
+    uint32_t refused, pad_[3];  // the second plan: the outputs do not fit, nothing is written
+};
+struct WireSeqWs : WireWs {
+    WireSeqPlan *plan;
+    dv_wire_seq_result *sres;  // (res, as the record it holds here)
+    uint64_t *mmask;           // [nb * kWireMaxMsg] a message's participants
+    uint16_t *msz;             // [nb * kWireMaxMsg] its bytes
+    uint32_t *dcnt, *dbyt;     // [nodes * nb] a destination's messages / bytes in mbuf b, then those in front of it
+    uint32_t *dtot, *dtotb;    // [nodes] a destination's messages / their bytes
+    uint32_t *dmb, *dMB;       // [nodes] its mbufs / the mbufs in front of its first
+    uint64_t *dDB;             // [nodes] the bytes in front of its first mbuf
+    uint32_t *lS;              // [n_list] a list entry's bytes in front of it in its destination
+    uint32_t *ljmp;            // [n_list] from this entry: mbufs opened inside its tile << 8 | where the walk leaves it
+    uint64_t *lpos;            // [n_list] the entry's byte in out
+    uint32_t *tent, *tmb;      // [nodes * n_tile] where the walk enters a tile, the destination's mbufs in front of it
+};
+static_assert(sizeof(dv_wire_seq_result) <= kWireResBytes, "the context's pinned words");
+
+// the list entries and tiles per destination that nb mbufs of at most max_txn txns can need
+inline uint64_t wire_seq_list_cap(uint32_t nb, uint32_t nodes, uint32_t max_txn) {
+    const uint64_t per_mbuf = kSeqMbufParts < (uint64_t)kWireMaxMsg * nodes ? kSeqMbufParts : (uint64_t)kWireMaxMsg * nodes;
+    const uint64_t per_txn = nodes < 128 ? nodes : 128;
+    const uint64_t a = nb * per_mbuf, b = max_txn * per_txn;
+    return (a < b ? a : b) + 2ull * nodes;
+}
+inline uint32_t wire_seq_tiles(uint32_t nb, uint32_t max_txn) {
+    const uint64_t a = (uint64_t)nb * kWireMaxMsg, t = a < max_txn ? a : max_txn;
+    return (uint32_t)((t + 1 + kSeqTile - 1) / kSeqTile);
+}
+
 // field f: n elements at the cursor, which moves on to the next multiple of 8 bytes
 template <class T>
 inline void wire_ws_field(char *base, uint64_t &at, T *&f, uint64_t n) {
@@ -59,7 +105,8 @@ inline void wire_ws_field(char *base, uint64_t &at, T *&f, uint64_t n) {
 // The one description of both workspaces: w's fields -- and, for CALVIN, c's
 // own (c is w) -- for nb batches (0 as 1) of `stride` messages.  Returns the
 // bytes they take; with a base it also points every field into it.
-inline uint64_t wire_ws_walk(void *base_, uint32_t nb, uint32_t stride, WireWs &w, WireCalvinWs *c) {
+inline uint64_t wire_ws_walk(void *base_, uint32_t nb, uint32_t stride, WireWs &w, WireCalvinWs *c,
+                             WireSeqWs *q = nullptr, uint32_t nodes = 0, uint32_t max_txn = 0) {
     const uint64_t n = nb ? nb : 1, nc = (n + kWireChunk - 1) / kWireChunk;
     char *base = static_cast<char *>(base_);
     uint64_t at = 0;
@@ -80,6 +127,27 @@ inline uint64_t wire_ws_walk(void *base_, uint32_t nb, uint32_t stride, WireWs &
     wire_ws_field(base, at, w.bm, n);
     if (c) wire_ws_field(base, at, c->brun, n);
     if (c) wire_ws_field(base, at, c->bflag, n);
+    if (!q) return at;
+    // the sequencer's own (q is w): nodes destinations, lists of wire_seq_list_cap entries
+    const uint64_t nl = wire_seq_list_cap((uint32_t)n, nodes, max_txn), ntile = wire_seq_tiles((uint32_t)n, max_txn);
+    q->sres = reinterpret_cast<dv_wire_seq_result *>(res);
+    uint8_t *plan;
+    wire_ws_field(base, at, plan, sizeof(WireSeqPlan));
+    q->plan = reinterpret_cast<WireSeqPlan *>(plan);
+    wire_ws_field(base, at, q->mmask, n * stride);
+    wire_ws_field(base, at, q->msz, n * stride);
+    wire_ws_field(base, at, q->dcnt, n * nodes);
+    wire_ws_field(base, at, q->dbyt, n * nodes);
+    wire_ws_field(base, at, q->dtot, nodes);
+    wire_ws_field(base, at, q->dtotb, nodes);
+    wire_ws_field(base, at, q->dmb, nodes);
+    wire_ws_field(base, at, q->dMB, nodes);
+    wire_ws_field(base, at, q->dDB, nodes);
+    wire_ws_field(base, at, q->lS, nl);
+    wire_ws_field(base, at, q->ljmp, nl);
+    wire_ws_field(base, at, q->lpos, nl);
+    wire_ws_field(base, at, q->tent, ntile * nodes);
+    wire_ws_field(base, at, q->tmb, ntile * nodes);
     return at;
 }
 
@@ -109,12 +177,59 @@ inline uint64_t reply_ws_layout(void *base_, uint32_t nt, uint32_t n_dest, Reply
     return at;
 }
 
+// The sequencer's acks (dv_wire_sequence_acks_device): the reply packer's words
+// for the txns that can complete, then its own for nb ack mbufs against n_txn
+// wait-list entries.  [zeroed, zeroed + zeroed_bytes) is cleared per call.
+struct AckWs {
+    ReplyWs r;
+    dv_wire_seq_ack_result *ares;  // kWireResBytes
+    uint32_t *first;               // the first malformed mbuf
+    uint8_t *zeroed;
+    uint64_t zeroed_bytes;
+    uint32_t *err2;                // a txn over-acked, a completed txn's client out of range
+    uint32_t *counts;              // acks of the batch, of other batches, completed txns
+    uint32_t *acnt, *alast;        // [n_txn] a txn's acks in the call, the position of its last
+    uint32_t *bt;                  // [nb] completing acks of the mbuf, then those in front of it
+    uint32_t *done;                // [n_cap] the completed txns in completing order
+};
+static_assert(sizeof(dv_wire_seq_ack_result) <= kWireResBytes, "the context's pinned words");
+
+// the txns nb mbufs of at most 46 acks can complete
+inline uint32_t ack_done_cap(uint32_t nb, uint32_t n_txn) {
+    const uint64_t a = (uint64_t)nb * 46;
+    return a < n_txn ? (uint32_t)a : n_txn;
+}
+
+inline uint64_t ack_ws_layout(void *base_, uint32_t nb, uint32_t n_txn, uint32_t n_dest, AckWs &w) {
+    char *base = static_cast<char *>(base_);
+    const uint32_t n_cap = ack_done_cap(nb, n_txn);
+    uint64_t at = reply_ws_layout(base_, (n_cap + kReplyTile - 1) / kReplyTile, n_dest, w.r);
+    uint8_t *res;
+    wire_ws_field(base, at, res, kWireResBytes);
+    w.ares = reinterpret_cast<dv_wire_seq_ack_result *>(res);
+    wire_ws_field(base, at, w.first, 2);
+    const uint64_t z0 = at;
+    wire_ws_field(base, at, w.zeroed, 0);
+    wire_ws_field(base, at, w.err2, 2);
+    wire_ws_field(base, at, w.counts, 4);
+    wire_ws_field(base, at, w.acnt, n_txn ? n_txn : 1);
+    wire_ws_field(base, at, w.alast, n_txn ? n_txn : 1);
+    w.zeroed_bytes = at - z0;
+    wire_ws_field(base, at, w.bt, nb ? nb : 1);
+    wire_ws_field(base, at, w.done, n_cap ? n_cap : 1);
+    return at;
+}
+
 inline uint64_t wire_ws_layout(void *base, uint32_t nb, WireWs &w) {
     return wire_ws_walk(base, nb, kWireMaxMsg, w, nullptr);
 }
 
 inline uint64_t wire_calvin_ws_layout(void *base, uint32_t nb, WireCalvinWs &w) {
     return wire_ws_walk(base, nb, kWireCalvinMaxMsg, w, &w);
+}
+
+inline uint64_t wire_seq_ws_layout(void *base, uint32_t nb, uint32_t nodes, uint32_t max_txn, WireSeqWs &w) {
+    return wire_ws_walk(base, nb, kWireMaxMsg, w, nullptr, &w, nodes, max_txn);
 }
 
 }  // namespace dvcc

@@ -325,3 +325,254 @@ extern "C" int dv_wire_respond(const dv_wire_cfg *cfg, const dv_wire_epoch *ep, 
     *n_batches = nb;
     return DV_OK;
 }
+
+// ---- the CALVIN sequencer (system/sequencer.cpp) on the host: the yardstick
+// of dv_wire_sequence_device / dv_wire_sequence_acks_device (dvcc_wire.hip).
+namespace {
+
+constexpr uint64_t kSeqHdr = 84;          // a CALVIN build's Message header
+constexpr uint64_t kAckBytes = 88;        // AckMessage: header + RC
+constexpr uint64_t kSeqRspBytes = 92;     // ClientResponseMessage: header + client_startts
+constexpr uint32_t kAckPer = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / kAckBytes;  // 46
+
+bool seq_cfg_ok(const dv_wire_cfg *c) {
+    return c && c->workload == DV_YCSB && c->calvin == 1 && c->part_cnt && c->node_cnt &&
+           c->node_cnt <= DV_WIRE_SEQ_NODE_MAX && c->node_id < c->node_cnt;
+}
+
+// mbuf b of the queue: its bytes, false where off decreases, points past the
+// buffer, or the length is outside [12, 4096]
+bool seq_span(const uint64_t *off, uint32_t b, uint64_t buf_len, uint64_t &o0, uint64_t &len) {
+    o0 = off[b];
+    const uint64_t o1 = off[b + 1];
+    if (o1 < o0 || o1 > buf_len || o1 - o0 < DV_WIRE_HDR || o1 - o0 > DV_WIRE_MSG_MAX) return false;
+    len = o1 - o0;
+    return true;
+}
+
+struct SeqTxn {
+    const uint8_t *msg;  // the client's message
+    uint32_t len, src;
+    uint64_t cst, parts;
+};
+
+// a client mbuf's txns appended to `txns`; false (and nothing appended) where it is malformed
+bool seq_client_mbuf(const dv_wire_cfg *cfg, uint32_t n_dest, const uint8_t *p, uint64_t len,
+                     std::vector<SeqTxn> &txns) {
+    uint32_t h[3];
+    std::memcpy(h, p, sizeof(h));
+    if (h[0] != cfg->node_id || h[1] < cfg->node_cnt || h[1] >= n_dest || h[2] == 0) return false;
+    const size_t keep = txns.size();
+    Reader r{p + DV_WIRE_HDR, p + len};
+    for (uint32_t i = 0; i < h[2]; i++) {
+        Msg m;
+        const uint8_t *at = r.p;
+        // (the message's own txn_id and batch_id are not looked at: a client sends UINT64_MAX in both)
+        const bool ok = read_client_part(cfg, r, m, true) && m.rtype == DV_WIRE_CL_QRY && read_ycsb(cfg, r, m, true) &&
+                        m.n_acc > 0;
+        if (!ok) {
+            txns.resize(keep);
+            return false;
+        }
+        uint64_t parts = 0;  // YCSBQuery::participants: GET_NODE_ID(key_to_part(key))
+        for (uint32_t q = 0; q < m.n_acc; q++) {
+            uint64_t key;
+            std::memcpy(&key, m.reqs + q * kYcsbReq + 8, 8);
+            parts |= 1ull << ((key % cfg->part_cnt) % cfg->node_cnt);
+        }
+        txns.push_back(SeqTxn{at, (uint32_t)(r.p - at), h[1], m.client_startts, parts});
+    }
+    if (r.p != p + len) {
+        txns.resize(keep);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int dv_wire_sequence(const dv_wire_cfg *cfg, const dv_wire_seq_in *in, const dv_wire_seq_out *out,
+                                dv_wire_seq_result *res) {
+    if (!seq_cfg_ok(cfg) || !in || !out || !res || !in->buf || !in->off) return DV_ERR_ARG;
+    if (!out->out || !out->batch_off || !out->dest_first || !out->wait_client || !out->wait_startts || !out->wait_acks)
+        return DV_ERR_ARG;
+    if (in->batch_id == kU64Max || !in->max_txn || in->first_batch > in->n_batches) return DV_ERR_ARG;
+    if (in->n_dest < cfg->node_cnt || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;
+    // the mbufs taken
+    std::vector<SeqTxn> txns;
+    int status = DV_OK;
+    uint32_t b = in->first_batch;
+    for (; b < in->n_batches; b++) {
+        uint64_t o0, len;
+        const size_t before = txns.size();
+        if (!seq_span(in->off, b, in->buf_len, o0, len) || !seq_client_mbuf(cfg, in->n_dest, in->buf + o0, len, txns)) {
+            status = DV_ERR_ARG;
+            break;
+        }
+        if (txns.size() > in->max_txn) {
+            txns.resize(before);
+            status = b == in->first_batch ? DV_ERR_ARG : DV_WIRE_MORE;
+            break;
+        }
+    }
+    // every destination's mbufs: MessageThread::run's greedy cut over its messages and the RDONE
+    const uint32_t nodes = cfg->node_cnt;
+    struct Mbuf { uint32_t dest, first, count; uint64_t at; };  // its messages: the destination's [first, first + count)
+    std::vector<std::vector<uint32_t>> list(nodes);             // a destination's txns
+    std::vector<Mbuf> mb;
+    uint64_t pos = 0, n_msgs = 0;
+    for (uint32_t k = 0; k < txns.size(); k++)
+        for (uint32_t d = 0; d < nodes; d++)
+            if (txns[k].parts >> d & 1) list[d].push_back(k), n_msgs++;
+    std::vector<uint32_t> dest_first(nodes + 1);
+    for (uint32_t d = 0; d < nodes; d++) {
+        dest_first[d] = (uint32_t)mb.size();
+        const uint32_t n = (uint32_t)list[d].size();
+        uint64_t size = DV_WIRE_MSG_MAX + 1;  // (no mbuf open)
+        for (uint32_t i = 0; i <= n; i++) {   // (i == n: the RDONE)
+            const uint64_t len = i < n ? txns[list[d][i]].len : kSeqHdr;
+            if (size + len > DV_WIRE_MSG_MAX) {
+                mb.push_back(Mbuf{d, i, 0, pos});
+                size = DV_WIRE_HDR;
+                pos += DV_WIRE_HDR;
+            }
+            mb.back().count++;
+            size += len;
+            pos += len;
+        }
+    }
+    dest_first[nodes] = (uint32_t)mb.size();
+    res->n_taken = b;
+    res->n_txn = (uint32_t)txns.size();
+    res->n_out = (uint32_t)mb.size();
+    res->n_msgs = n_msgs;
+    res->n_bytes = pos;
+    if (pos > out->cap || mb.size() > out->max_batches) return res->status = DV_ERR_ARG;  // (nothing written)
+    res->status = status;
+    for (uint32_t k = 0; k < txns.size(); k++) {
+        out->wait_client[k] = txns[k].src;
+        out->wait_startts[k] = txns[k].cst;
+        out->wait_acks[k] = (uint32_t)__builtin_popcountll(txns[k].parts);
+    }
+    std::memcpy(out->dest_first, dest_first.data(), dest_first.size() * sizeof(uint32_t));
+    for (size_t j = 0; j < mb.size(); j++) {
+        const Mbuf &m = mb[j];
+        out->batch_off[j] = m.at;
+        Writer w{out->out + m.at};
+        w.put<uint32_t>(m.dest);
+        w.put<uint32_t>(cfg->node_id);
+        w.put<uint32_t>(m.count);
+        for (uint32_t i = m.first; i < m.first + m.count; i++) {
+            const bool done = i == list[m.dest].size();
+            const uint32_t k = done ? 0 : list[m.dest][i];
+            w.put<uint32_t>(done ? DV_WIRE_RDONE : DV_WIRE_CL_QRY);
+            w.put<uint64_t>(done ? kU64Max : cfg->node_id + (uint64_t)nodes * k);
+            w.put<uint64_t>(in->batch_id);
+            w.zeros(8 + 7 * 8);  // mq_time, latencies
+            if (!done) {
+                std::memcpy(w.p, txns[k].msg + kSeqHdr, txns[k].len - kSeqHdr);
+                w.p += txns[k].len - kSeqHdr;
+            }
+        }
+    }
+    out->batch_off[mb.size()] = pos;
+    return status;
+}
+
+extern "C" int dv_wire_sequence_acks(const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in, const dv_wire_rsp_out *out,
+                                     dv_wire_seq_ack_result *res) {
+    if (!seq_cfg_ok(cfg) || !in || !out || !res || !in->buf || !in->off || !out->out || !out->batch_off)
+        return DV_ERR_ARG;
+    if (in->n_txn && (!in->wait_client || !in->wait_startts || !in->wait_acks)) return DV_ERR_ARG;
+    if (in->batch_id == kU64Max || !in->n_dest || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;
+    *res = dv_wire_seq_ack_result{DV_ERR_ARG, DV_WIRE_NO_BATCH, 0, 0, 0, 0, 0};
+    // per txn: its acks in the call and the position of the last
+    std::vector<uint32_t> cnt(in->n_txn, 0);
+    std::vector<uint64_t> last(in->n_txn, 0);
+    uint64_t at = 0;  // the stream position: mbuf-major, message-minor
+    for (uint32_t b = 0; b < in->n_batches; b++) {
+        uint64_t o0, len;
+        bool ok = seq_span(in->off, b, in->buf_len, o0, len);
+        uint32_t h[3] = {0, 0, 0};
+        if (ok) {
+            std::memcpy(h, in->buf + o0, sizeof(h));
+            ok = h[0] == cfg->node_id && h[1] < cfg->node_cnt && h[2] >= 1 && h[2] <= kAckPer &&
+                 len == DV_WIRE_HDR + kAckBytes * h[2];
+        }
+        for (uint32_t m = 0; ok && m < h[2]; m++, at++) {
+            const uint8_t *p = in->buf + o0 + DV_WIRE_HDR + m * kAckBytes;
+            uint32_t rtype;
+            uint64_t txn_id, bid;
+            std::memcpy(&rtype, p, 4);
+            std::memcpy(&txn_id, p + 4, 8);
+            std::memcpy(&bid, p + 12, 8);
+            if (rtype != DV_WIRE_CALVIN_ACK || bid == kU64Max) {
+                ok = false;
+            } else if (bid != in->batch_id) {
+                res->n_skipped++;
+            } else if (txn_id % cfg->node_cnt != cfg->node_id || txn_id / cfg->node_cnt >= in->n_txn) {
+                ok = false;
+            } else {
+                const uint64_t k = txn_id / cfg->node_cnt;
+                cnt[k]++;
+                last[k] = at;
+                res->n_acks++;
+            }
+        }
+        if (!ok) {
+            *res = dv_wire_seq_ack_result{DV_ERR_ARG, b, 0, 0, 0, 0, 0};
+            return DV_ERR_ARG;
+        }
+    }
+    // (a refused call reports no count, but for replies that do not fit)
+    const auto refuse = [&] {
+        *res = dv_wire_seq_ack_result{DV_ERR_ARG, DV_WIRE_NO_BATCH, 0, 0, 0, 0, 0};
+        return DV_ERR_ARG;
+    };
+    // the txns that complete, in the order of their last acks
+    std::vector<uint32_t> done;
+    for (uint32_t k = 0; k < in->n_txn; k++) {
+        if (cnt[k] > in->wait_acks[k]) return refuse();  // assert(server_ack_cnt > 0)
+        if (cnt[k] && cnt[k] == in->wait_acks[k]) {
+            if (in->wait_client[k] >= in->n_dest) return refuse();
+            done.push_back(k);
+        }
+    }
+    std::sort(done.begin(), done.end(), [&](uint32_t a, uint32_t c) { return last[a] < last[c]; });
+    std::stable_sort(done.begin(), done.end(),
+                     [&](uint32_t a, uint32_t c) { return in->wait_client[a] < in->wait_client[c]; });
+    // dv_wire_respond's packing of 92-byte CL_RSPs, decided before anything is written
+    const uint32_t per = (uint32_t)((DV_WIRE_MSG_MAX - DV_WIRE_HDR) / kSeqRspBytes);
+    uint32_t nb = 0;
+    for (size_t i = 0, j; i < done.size(); i = j, nb++)
+        for (j = i; j < done.size() && j - i < per && in->wait_client[done[j]] == in->wait_client[done[i]];) j++;
+    res->n_done = (uint32_t)done.size();
+    res->n_batches = nb;
+    res->n_bytes = (uint64_t)nb * DV_WIRE_HDR + done.size() * kSeqRspBytes;
+    if (res->n_bytes > out->cap || nb > out->max_batches) return DV_ERR_ARG;
+    for (uint32_t k = 0; k < in->n_txn; k++) in->wait_acks[k] -= cnt[k];
+    uint64_t pos = 0;
+    nb = 0;
+    out->batch_off[0] = 0;
+    for (size_t i = 0, j; i < done.size(); i = j) {
+        const uint32_t dest = in->wait_client[done[i]];
+        for (j = i; j < done.size() && j - i < per && in->wait_client[done[j]] == dest;) j++;
+        Writer w{out->out + pos};
+        w.put<uint32_t>(dest);
+        w.put<uint32_t>(cfg->node_id);
+        w.put<uint32_t>((uint32_t)(j - i));
+        for (size_t q = i; q < j; q++) {
+            w.put<uint32_t>(DV_WIRE_CL_RSP);
+            w.put<uint64_t>(cfg->node_id + (uint64_t)cfg->node_cnt * done[q]);
+            w.put<uint64_t>(kU64Max);  // batch_id (message.cpp:99-103, 178)
+            w.zeros(8 + 7 * 8);
+            w.put<uint64_t>(in->wait_startts[done[q]]);
+        }
+        pos += DV_WIRE_HDR + (j - i) * kSeqRspBytes;
+        out->batch_off[++nb] = pos;
+    }
+    res->status = DV_OK;
+    return DV_OK;
+}

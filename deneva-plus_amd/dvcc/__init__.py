@@ -24,3 +24,4 @@ from .engine import CCEngine, ClosedLoopBufs, DeviceEpoch, Epoch, LoopBackoff, L
 from .tpcc import TpccEngine, TpccLoopBackoff, TpccLoopBufs  # noqa: F401
 from .ycsb import YCSBQueryGenerator, epoch_seed, sequence, sequence_position  # noqa: F401
 from .wire import CalvinDeviceWireIngress, DeviceWireIngress, TpccDeviceWireIngress, WireIngress  # noqa: F401,E402
+from .wire import DeviceSequencer  # noqa: F401,E402

@@ -195,6 +195,40 @@ class WireRspResult(ctypes.Structure):  # dv_wire_rsp_result
                 ("pad_", ctypes.c_uint32), ("n_bytes", ctypes.c_uint64)]
 
 
+WIRE_SEQ_NODE_MAX = 64
+WIRE_NO_BATCH = 0xFFFFFFFF
+
+
+class WireSeqIn(ctypes.Structure):  # dv_wire_seq_in: a receive queue of client mbufs for dv_wire_sequence[_device]
+    _fields_ = [("buf", ctypes.c_void_p), ("buf_len", ctypes.c_uint64), ("off", ctypes.c_void_p),
+                ("n_batches", ctypes.c_uint32), ("first_batch", ctypes.c_uint32), ("batch_id", ctypes.c_uint64),
+                ("n_dest", ctypes.c_uint32), ("max_txn", ctypes.c_uint32)]
+
+
+class WireSeqOut(ctypes.Structure):  # dv_wire_seq_out: the outgoing mbufs and the wait list
+    _fields_ = [("out", ctypes.c_void_p), ("cap", ctypes.c_uint64), ("batch_off", ctypes.c_void_p),
+                ("max_batches", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("dest_first", ctypes.c_void_p),
+                ("wait_client", ctypes.c_void_p), ("wait_startts", ctypes.c_void_p), ("wait_acks", ctypes.c_void_p)]
+
+
+class WireSeqResult(ctypes.Structure):  # dv_wire_seq_result
+    _fields_ = [("status", ctypes.c_int32), ("n_taken", ctypes.c_uint32), ("n_txn", ctypes.c_uint32),
+                ("n_out", ctypes.c_uint32), ("n_msgs", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64)]
+
+
+class WireSeqAckIn(ctypes.Structure):  # dv_wire_seq_ack_in: ack mbufs and the wait list they count against
+    _fields_ = [("buf", ctypes.c_void_p), ("buf_len", ctypes.c_uint64), ("off", ctypes.c_void_p),
+                ("n_batches", ctypes.c_uint32), ("n_dest", ctypes.c_uint32), ("batch_id", ctypes.c_uint64),
+                ("n_txn", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("wait_client", ctypes.c_void_p),
+                ("wait_startts", ctypes.c_void_p), ("wait_acks", ctypes.c_void_p)]
+
+
+class WireSeqAckResult(ctypes.Structure):  # dv_wire_seq_ack_result
+    _fields_ = [("status", ctypes.c_int32), ("first_bad", ctypes.c_uint32), ("n_acks", ctypes.c_uint32),
+                ("n_skipped", ctypes.c_uint32), ("n_done", ctypes.c_uint32), ("n_batches", ctypes.c_uint32),
+                ("n_bytes", ctypes.c_uint64)]
+
+
 # dv_wire_calvin_pos::stop (DV_WIRE_STOP_*)
 WIRE_STOP_END, WIRE_STOP_BATCH, WIRE_STOP_CAPACITY, WIRE_STOP_WINDOW, WIRE_STOP_MALFORMED, WIRE_STOP_STALE = range(6)
 WIRE_NO_BATCH_ID = (1 << 64) - 1
@@ -326,6 +360,11 @@ SIGNATURES = [
     ("dv_wire_reply_fields_device", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _P(ctypes.c_uint32)]),
     ("dv_wire_respond_device", ctypes.c_int, [_vp, _P(WireCfg), _P(WireRspIn), _P(WireRspOut), _P(WireRspResult)]),
+    ("dv_wire_sequence", ctypes.c_int, [_P(WireCfg), _P(WireSeqIn), _P(WireSeqOut), _P(WireSeqResult)]),
+    ("dv_wire_sequence_device", ctypes.c_int, [_vp, _P(WireCfg), _P(WireSeqIn), _P(WireSeqOut), _P(WireSeqResult)]),
+    ("dv_wire_sequence_acks", ctypes.c_int, [_P(WireCfg), _P(WireSeqAckIn), _P(WireRspOut), _P(WireSeqAckResult)]),
+    ("dv_wire_sequence_acks_device", ctypes.c_int, [_vp, _P(WireCfg), _P(WireSeqAckIn), _P(WireRspOut),
+                                                    _P(WireSeqAckResult)]),
     ("dv_epoch_reads_tb_only", ctypes.c_int, [_vp, ctypes.c_uint32]),
     ("dv_closed_loop_track", ctypes.c_int, [_vp, _P(LoopTrackDesc)]),
     ("dv_closed_loop_backoff", ctypes.c_int, [_vp, _P(LoopBackoffDesc)]),

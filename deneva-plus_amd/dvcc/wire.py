@@ -604,6 +604,184 @@ class CalvinTpccDeviceWireIngress(_CalvinStreams):
         return ep
 
 
+def _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req):
+    return L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
+
+
+def _seq_room(in_bytes, node_cnt):
+    """(cap, max_batches) that the fan-out of in_bytes of client mbufs cannot
+    pass: every message to every node, two consecutive mbufs of a destination
+    hold more than 4,084 message bytes, an RDONE and a last mbuf per node."""
+    msgs = in_bytes * node_cnt
+    max_b = 2 * msgs // (L.WIRE_MSG_MAX - L.WIRE_HDR) + 2 * node_cnt
+    return msgs + 84 * node_cnt + L.WIRE_HDR * max_b, max_b
+
+
+_ACK_MSG, _SEQ_RSP_MSG = 88, 92  # AckMessage, ClientResponseMessage of a CALVIN build
+
+
+def _seq_rsp_room(n, n_dest):
+    """(cap, max_batches) for n CL_RSPs to n_dest destinations"""
+    max_b = n // ((L.WIRE_MSG_MAX - L.WIRE_HDR) // _SEQ_RSP_MSG) + min(n, n_dest) + 1
+    return max_b * L.WIRE_HDR + n * _SEQ_RSP_MSG, max_b
+
+
+@dataclass
+class SequencedBatch:
+    """What dv_wire_sequence wrote (host arrays at their full capacity):
+    mbuf j at out[batch_off[j]:batch_off[j + 1]], destination d's mbufs
+    dest_first[d] .. dest_first[d + 1] - 1, the wait list's first n_txn
+    entries, and the result record."""
+    out: np.ndarray
+    batch_off: np.ndarray
+    dest_first: np.ndarray
+    wait_client: np.ndarray
+    wait_startts: np.ndarray
+    wait_acks: np.ndarray
+    result: object
+
+    def mbufs(self, dest=None):
+        """the outgoing mbufs (bytes), all or one destination's"""
+        lo, hi = (0, self.result.n_out) if dest is None else (int(self.dest_first[dest]), int(self.dest_first[dest + 1]))
+        return [self.out[int(self.batch_off[j]):int(self.batch_off[j + 1])].tobytes() for j in range(lo, hi)]
+
+
+def sequence_host(buf, off, batch_id, *, node_id, node_cnt, part_cnt, synth_table_size, n_dest, max_txn, max_req=0,
+                  first_batch=0, cap=None, max_batches=None):
+    """dv_wire_sequence over numpy arrays: the client mbufs first_batch.. of
+    buf (uint8) at offsets off (u64 [n + 1]) stamped as batch batch_id of
+    sequencer node_id and fanned out -> SequencedBatch.  cap / max_batches
+    default to what the input cannot pass.  A call the library refuses before
+    it looks at the bytes raises; result.status holds every other outcome."""
+    buf, off = np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(off, np.uint64)
+    blen = len(buf)
+    if not blen:
+        buf = np.zeros(1, np.uint8)  # (an empty queue still has an address)
+    cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req)
+    room = _seq_room(blen, node_cnt)
+    cap, max_b = room[0] if cap is None else cap, room[1] if max_batches is None else max_batches
+    b = SequencedBatch(np.zeros(max(cap, 4), np.uint8), np.zeros(max_b + 1, np.uint64),
+                       np.zeros(node_cnt + 1, np.uint32), np.zeros(max(1, max_txn), np.uint32),
+                       np.zeros(max(1, max_txn), np.uint64), np.zeros(max(1, max_txn), np.uint32),
+                       L.WireSeqResult(status=-1000))
+    sin = L.WireSeqIn(buf.ctypes.data, blen, off.ctypes.data, len(off) - 1, first_batch, batch_id, n_dest, max_txn)
+    sout = L.WireSeqOut(b.out.ctypes.data, cap, b.batch_off.ctypes.data, max_b, 0, b.dest_first.ctypes.data,
+                        b.wait_client.ctypes.data, b.wait_startts.ctypes.data, b.wait_acks.ctypes.data)
+    rc = L.lib().dv_wire_sequence(ctypes.byref(cfg), ctypes.byref(sin), ctypes.byref(sout), ctypes.byref(b.result))
+    if b.result.status != rc:
+        L.check(rc, "dv_wire_sequence")
+    return b
+
+
+def sequence_acks_host(buf, off, batch_id, wait_client, wait_startts, wait_acks, *, node_id, node_cnt, n_dest,
+                       part_cnt=1, cap=None, max_batches=None):
+    """dv_wire_sequence_acks over numpy arrays: the ack mbufs of buf / off
+    counted against batch batch_id's wait list (wait_acks, uint32, is updated
+    in place) -> (out, batch_off, result), the CL_RSP mbufs of the txns that
+    completed at out[batch_off[j]:batch_off[j + 1]], j < result.n_batches."""
+    buf, off = np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(off, np.uint64)
+    blen = len(buf)
+    if not blen:
+        buf = np.zeros(1, np.uint8)
+    assert wait_acks.dtype == np.uint32 and wait_acks.flags.c_contiguous
+    wc, ws = np.ascontiguousarray(wait_client, np.uint32), np.ascontiguousarray(wait_startts, np.uint64)
+    n = len(wait_acks)
+    cfg = _seq_cfg(node_id, node_cnt, part_cnt, 0, 0)
+    room = _seq_rsp_room(n, n_dest)
+    cap, max_b = room[0] if cap is None else cap, room[1] if max_batches is None else max_batches
+    out, boff = np.zeros(max(cap, 4), np.uint8), np.zeros(max_b + 1, np.uint64)
+    ain = L.WireSeqAckIn(buf.ctypes.data, blen, off.ctypes.data, len(off) - 1, n_dest, batch_id, n, 0,
+                         wc.ctypes.data, ws.ctypes.data, wait_acks.ctypes.data)
+    rout = L.WireRspOut(out.ctypes.data, cap, boff.ctypes.data, max_b, 0)
+    res = L.WireSeqAckResult(status=-1000)
+    rc = L.lib().dv_wire_sequence_acks(ctypes.byref(cfg), ctypes.byref(ain), ctypes.byref(rout), ctypes.byref(res))
+    if res.status != rc:
+        L.check(rc, "dv_wire_sequence_acks")
+    return out, boff, res
+
+
+class DeviceSequencer:
+    """The CALVIN sequencer of node node_id on `engine`'s context and stream
+    (dv_wire_sequence_device / dv_wire_sequence_acks_device, YCSB).  It owns
+    the wait list of the batch it sequenced last (wait_client, wait_startts,
+    wait_acks: device tensors of max_txn entries, n_txn of them live) and the
+    output tensors, which the next call of the same kind overwrites.  cap /
+    max_batches bound the outgoing bytes and mbufs of sequence(); by default
+    they are what the call's input cannot pass."""
+
+    def __init__(self, engine, node_id, node_cnt, part_cnt, synth_table_size, max_req, max_txn, n_dest, cap=None,
+                 max_batches=None, device="cuda"):
+        import torch
+        self.engine, self._dev = engine, device
+        self.cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req)
+        self.node_id, self.node_cnt, self.n_dest, self.max_txn = node_id, node_cnt, n_dest, int(max_txn)
+        self.cap, self.max_batches = cap, max_batches
+        new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=device)  # noqa: E731
+        self.wait_client, self.wait_acks = new(self.max_txn, torch.int32), new(self.max_txn, torch.int32)
+        self.wait_startts = new(self.max_txn, torch.int64)
+        self.dest_first = new(node_cnt + 1, torch.int32)
+        self.batch_id, self.n_txn = None, 0
+        self._out = self._off = self._rsp_out = self._rsp_off = None
+
+    def _grown(self, t, n, dtype):
+        import torch
+        return t if t is not None and t.numel() >= n else torch.empty(n, dtype=dtype, device=self._dev)
+
+    def sequence(self, buf, off, batch_id, first_batch=0):
+        """The client mbufs first_batch.. of buf (a torch uint8 device tensor,
+        or a numpy array, uploaded) at offsets off become batch batch_id ->
+        (out, batch_off, dest_first, result): device tensors written on the
+        engine's stream, of exact size where the call wrote them, and the
+        result record (status DV_OK, WIRE_MORE: call again from n_taken for
+        the next batch, or DV_ERR_ARG)."""
+        import torch
+        buf, off = _DeviceIngress._upload(buf, off, self._dev)
+        room = _seq_room(buf.numel(), self.node_cnt)
+        cap, max_b = room[0] if self.cap is None else self.cap, room[1] if self.max_batches is None else self.max_batches
+        self._out = self._grown(self._out, max(cap, 4), torch.uint8)
+        self._off = self._grown(self._off, max_b + 1, torch.int64)
+        sin = L.WireSeqIn(buf.data_ptr(), buf.numel(), off.data_ptr(), off.numel() - 1, first_batch, batch_id,
+                          self.n_dest, self.max_txn)
+        sout = L.WireSeqOut(self._out.data_ptr(), cap, self._off.data_ptr(), max_b, 0, self.dest_first.data_ptr(),
+                            self.wait_client.data_ptr(), self.wait_startts.data_ptr(), self.wait_acks.data_ptr())
+        res = L.WireSeqResult(status=-1000)
+        self.engine._after_torch()
+        rc = L.lib().dv_wire_sequence_device(self.engine._ctx, ctypes.byref(self.cfg), ctypes.byref(sin),
+                                             ctypes.byref(sout), ctypes.byref(res))
+        _DeviceIngress._check(rc, res.status == rc, "dv_wire_sequence_device")
+        self._held = (buf, off)  # (the emit may still read them when this returns)
+        wrote = res.status != L.DV_ERR_ARG or (res.n_bytes <= cap and res.n_out <= max_b)
+        self.batch_id, self.n_txn = (batch_id, res.n_txn) if wrote else (None, 0)
+        if not wrote:
+            return self._out[:0], self._off[:0], self.dest_first[:0], res
+        return self._out[:res.n_bytes], self._off[:res.n_out + 1], self.dest_first, res
+
+    def acks(self, buf, off):
+        """The ack mbufs of buf / off counted against the wait list ->
+        (out, batch_off, n_batches, result): the CL_RSP mbufs of the txns whose
+        last ack came, as respond_device returns its replies."""
+        import torch
+        if self.batch_id is None:
+            raise L.DvccError(L.DV_ERR_ARG, "DeviceSequencer.acks: no batch sequenced")
+        buf, off = _DeviceIngress._upload(buf, off, self._dev)
+        cap, max_b = _seq_rsp_room(self.n_txn, self.n_dest)
+        self._rsp_out = self._grown(self._rsp_out, max(cap, 4), torch.uint8)
+        self._rsp_off = self._grown(self._rsp_off, max_b + 1, torch.int64)
+        ain = L.WireSeqAckIn(buf.data_ptr(), buf.numel(), off.data_ptr(), off.numel() - 1, self.n_dest, self.batch_id,
+                             self.n_txn, 0, self.wait_client.data_ptr(), self.wait_startts.data_ptr(),
+                             self.wait_acks.data_ptr())
+        rout = L.WireRspOut(self._rsp_out.data_ptr(), cap, self._rsp_off.data_ptr(), max_b, 0)
+        res = L.WireSeqAckResult(status=-1000)
+        self.engine._after_torch()
+        rc = L.lib().dv_wire_sequence_acks_device(self.engine._ctx, ctypes.byref(self.cfg), ctypes.byref(ain),
+                                                  ctypes.byref(rout), ctypes.byref(res))
+        _DeviceIngress._check(rc, res.status == rc, "dv_wire_sequence_acks_device")
+        self._ack_held = (buf, off)
+        if res.status != L.DV_OK:
+            return self._rsp_out[:0], self._rsp_off[:0], 0, res
+        return self._rsp_out[:res.n_bytes], self._rsp_off[:res.n_batches + 1], res.n_batches, res
+
+
 def tpcc_gen_queries(p, n_txn, seed, home_part=0):
     """dv_tpcc_gen_queries: the client queries of dv_tpcc_gen (same draws)."""
     q = (L.TpccQuery * max(1, n_txn))()

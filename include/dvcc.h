@@ -67,6 +67,9 @@
  *                               dv_wire_respond
  *   dv_wire_respond_device      dv_wire_respond's mbufs packed on the device from reply
  *                               fields in device memory (same reference lines)
+ *   dv_wire_sequence[_device] / a CALVIN sequencer's own role (system/sequencer.cpp:55-326,
+ *   dv_wire_sequence_acks[_device] YCSB): client CL_QRYs stamped, fanned out per participant
+ *                               and closed with RDONEs; CALVIN_ACKs counted, CL_RSPs sent
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
  * the final table state equal a single worker thread running the same epoch
@@ -1560,6 +1563,136 @@ typedef struct dv_wire_rsp_result {
  * A context in the middle of an epoch: DV_ERR_STATE. */
 int dv_wire_respond_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_rsp_in *in,
                            const dv_wire_rsp_out *out, dv_wire_rsp_result *res);
+
+/* ---- The CALVIN sequencer (system/sequencer.cpp): a server's own role under
+ * CALVIN, on the host (csrc/wire.cpp) and on the device (dvcc_wire.hip).
+ * dv_wire_sequence stamps one batch of client CL_QRYs and fans it out
+ * (Sequencer::process_txn / send_next_batch, sequencer.cpp:184-326);
+ * dv_wire_sequence_acks counts the servers' CALVIN_ACKs against the batch's
+ * wait list and answers the clients (Sequencer::process_ack, 55-181).  YCSB
+ * only: cfg->workload == DV_YCSB, cfg->calvin == 1, cfg->node_id <
+ * cfg->node_cnt <= DV_WIRE_SEQ_NODE_MAX (a txn's participants are one 64-bit
+ * mask).  The host functions take host pointers, the device functions device
+ * pointers (wait list included); the device functions write what the host
+ * functions write, bit for bit. */
+#define DV_WIRE_SEQ_NODE_MAX 64
+
+typedef struct dv_wire_seq_in {
+    const uint8_t *buf;            /* the receive queue: client mbufs back to back, any alignment */
+    uint64_t buf_len;
+    const uint64_t *off;           /* [n_batches + 1]: mbuf b at buf[off[b] .. off[b + 1])       */
+    uint32_t n_batches, first_batch;
+    uint64_t batch_id;             /* E; not UINT64_MAX                                          */
+    uint32_t n_dest;               /* g_node_cnt + g_client_node_cnt: node_cnt <= src < n_dest;
+                                      at most DV_WIRE_DEST_MAX                                   */
+    uint32_t max_txn;              /* entries of the wait list                                   */
+} dv_wire_seq_in;
+
+typedef struct dv_wire_seq_out {
+    uint8_t *out;                  /* the outgoing mbufs back to back, 4-byte aligned            */
+    uint64_t cap;
+    uint64_t *batch_off;           /* [max_batches + 1]                                          */
+    uint32_t max_batches, pad_;
+    uint32_t *dest_first;          /* [node_cnt + 1]: destination d's mbufs are dest_first[d] ..
+                                      dest_first[d + 1] - 1; dest_first[node_cnt] = n_out        */
+    uint32_t *wait_client;         /* [max_txn] the wait list: the client's node                 */
+    uint64_t *wait_startts;        /* [max_txn] its client_startts                               */
+    uint32_t *wait_acks;           /* [max_txn] acks outstanding: the txn's participants         */
+} dv_wire_seq_out;
+
+typedef struct dv_wire_seq_result {
+    int32_t status;                /* what the call returns: DV_OK, DV_WIRE_MORE, DV_ERR_ARG     */
+    uint32_t n_taken;              /* the first mbuf not taken (n_batches: all were)             */
+    uint32_t n_txn;
+    uint32_t n_out;                /* outgoing mbufs                                             */
+    uint64_t n_msgs;               /* CL_QRYs sent: the sum of the txns' participant counts      */
+    uint64_t n_bytes;
+} dv_wire_seq_result;
+
+/* Client mbufs first_batch .. are taken whole and in order.  A client mbuf has
+ * the CALVIN header (84 bytes: a CALVIN build's), dest == node_id, node_cnt <=
+ * src < n_dest (ISCLIENTN, sequencer.cpp:223), count >= 1, messages that fill
+ * its length exactly, every one a CL_QRY with what dv_wire_open checks of a
+ * YCSB CL_QRY and one request at least (sequencer.cpp:222); the message's own
+ * txn_id and batch_id are not looked at (a client sends UINT64_MAX in both).
+ * Taking ends where all are taken (DV_OK), where the next mbuf's txns pass
+ * max_txn (DV_WIRE_MORE, n_taken names it; DV_ERR_ARG when it is first_batch
+ * itself) or where the next is malformed (DV_ERR_ARG, n_taken names it; the
+ * mbufs in front of it are sequenced, no byte of it reaches an output).
+ * The k-th taken message is txn k of the batch: txn_id = node_id + node_cnt *
+ * k, batch_id = E, participants P_k = {(key % part_cnt) % node_cnt} over its
+ * requests (YCSBQuery::participants); wait_client[k] = its mbuf's src,
+ * wait_startts[k] = its client_startts, wait_acks[k] = |P_k|.  The outgoing
+ * message is the incoming one with txn_id and batch_id stamped, mq_time and the
+ * seven latencies zeroed, bytes 84 .. copied.  Destination d = 0 .. node_cnt - 1
+ * (the own node included) receives the messages of the txns with d in P_k in
+ * txn order, then one RDONE (the header alone, txn_id UINT64_MAX, batch_id E),
+ * packed as MessageThread::run packs: a 12-byte header {d, node_id, count}, a
+ * message that would pass 4,096 bytes opens the next mbuf.  A batch without a
+ * txn is node_cnt mbufs of one RDONE.
+ * Bytes against cap and mbufs against max_batches are decided before anything
+ * is written: such a call is DV_ERR_ARG, writes no byte of out, batch_off,
+ * dest_first or the wait list, and n_out / n_bytes hold what it needed
+ * (n_taken, n_txn, n_msgs what it would have taken).  Nothing is written at or
+ * past out[n_bytes], batch_off[n_out + 1] or wait-list entry n_txn.
+ * Refused with DV_ERR_ARG and *res untouched: a null pointer, another workload,
+ * calvin == 0, part_cnt == 0, node_id >= node_cnt, node_cnt >
+ * DV_WIRE_SEQ_NODE_MAX, n_dest < node_cnt or > DV_WIRE_DEST_MAX, batch_id
+ * UINT64_MAX, max_txn == 0, first_batch > n_batches, out not 4-byte aligned.
+ * The device call is queued on the context's stream and waits for the result
+ * record alone. */
+int dv_wire_sequence(const dv_wire_cfg *cfg, const dv_wire_seq_in *in, const dv_wire_seq_out *out,
+                     dv_wire_seq_result *res);
+int dv_wire_sequence_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_seq_in *in,
+                            const dv_wire_seq_out *out, dv_wire_seq_result *res);
+
+typedef struct dv_wire_seq_ack_in {
+    const uint8_t *buf;            /* ack mbufs back to back, any alignment                      */
+    uint64_t buf_len;
+    const uint64_t *off;           /* [n_batches + 1]                                            */
+    uint32_t n_batches;
+    uint32_t n_dest;               /* every answered client < n_dest; 1 .. DV_WIRE_DEST_MAX      */
+    uint64_t batch_id;             /* E: the batch the wait list belongs to                      */
+    uint32_t n_txn, pad_;          /* its txns                                                   */
+    const uint32_t *wait_client;   /* the wait list dv_wire_sequence wrote                       */
+    const uint64_t *wait_startts;
+    uint32_t *wait_acks;           /* in/out                                                     */
+} dv_wire_seq_ack_in;
+
+#define DV_WIRE_NO_BATCH 0xFFFFFFFFu
+
+typedef struct dv_wire_seq_ack_result {
+    int32_t status;                /* what the call returns: DV_OK or DV_ERR_ARG                 */
+    uint32_t first_bad;            /* the first malformed mbuf, DV_WIRE_NO_BATCH where none is   */
+    uint32_t n_acks;               /* acks of batch E in the call                                */
+    uint32_t n_skipped;            /* acks of other batches                                      */
+    uint32_t n_done;               /* txns whose last ack came: CL_RSPs packed                   */
+    uint32_t n_batches;
+    uint64_t n_bytes;
+} dv_wire_seq_ack_result;
+
+/* An ack mbuf has dest == node_id, src < node_cnt (the own node's acks come as
+ * an mbuf like the others), 1 <= count <= 46, length 12 + 88 * count, every
+ * message a CALVIN_ACK whose batch id is not UINT64_MAX.  A message of another
+ * batch id is skipped (n_skipped); one of batch E must name a txn of this
+ * sequencer (txn_id % node_cnt == node_id, txn_id / node_cnt < n_txn), else its
+ * mbuf is malformed.  rc is not read.  All or nothing: with a malformed mbuf
+ * (first_bad), a txn that gets more acks in the call than wait_acks[k] holds,
+ * a completed txn's wait_client[k] >= n_dest, or replies that pass out->cap /
+ * out->max_batches (n_batches / n_bytes then hold what they need) the call is
+ * DV_ERR_ARG, the wait list is untouched and no output byte is written.
+ * Otherwise wait_acks[k] drops by the txn's acks in the call; a txn that
+ * reaches 0 completes at the stream position (mbuf-major, message-minor) of its
+ * last ack, and the completed txns are answered in ascending completing
+ * position, each with a CL_RSP in the CALVIN build's layout (92 bytes, 44 to a
+ * full mbuf) to wait_client[k]: txn_id = node_id + node_cnt * k, batch_id
+ * UINT64_MAX, client_startts = wait_startts[k].  Packed as
+ * dv_wire_respond_device packs: destinations ascending, a destination's
+ * replies in that order; out, batch_off, cap and max_batches as there. */
+int dv_wire_sequence_acks(const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in, const dv_wire_rsp_out *out,
+                          dv_wire_seq_ack_result *res);
+int dv_wire_sequence_acks_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in,
+                                 const dv_wire_rsp_out *out, dv_wire_seq_ack_result *res);
 
 /* 1 when an epoch of n_txn txns given as records and boundaries alone
  * (recs32, txn_begin, n_acc_dev) would take this context's tb-mode
