@@ -60,12 +60,14 @@ class Epoch:
         return np.repeat(np.arange(self.n_txn, dtype=np.uint32), counts)
 
     def to_row_records(self):
-        """4-byte records for dv_epoch_stage_host_rows: key | write << 31
-        (table 0 reads / writes, keys below 2^31)"""
-        if self.n_acc and (int(self.keys.max()) >> 31 or (self.types > 1).any()
+        """4-byte records for dv_epoch_stage_host_rows: key | (type == WR) << 31
+        (table 0 reads / writes, keys below 2^31).  A SCAN is a shared access
+        that reads the row (row.cpp:191, ycsb_txn.cpp:228): its write bit is
+        clear, and the record no longer tells it from a RD."""
+        if self.n_acc and (int(self.keys.max()) >> 31 or (~np.isin(self.types, (L.RD, L.WR, L.SCAN))).any()
                            or (self.tables is not None and self.tables.any())):
             raise ValueError("4-byte records hold table-0 reads / writes of keys below 2^31")
-        return (self.keys.astype(np.uint32) | (self.types.astype(np.uint32) << 31)).astype(np.uint32)
+        return (self.keys.astype(np.uint32) | ((self.types == L.WR).astype(np.uint32) << 31)).astype(np.uint32)
 
     def to_access_array(self):
         a = np.zeros(self.n_acc, dtype=[("key", "<u8"), ("txn_seq", "<u4"), ("type", "u1"),

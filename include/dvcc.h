@@ -111,7 +111,9 @@ extern "C" {
 /* access_t (system/global.h:287) */
 #define DV_RD 0
 #define DV_WR 1
-#define DV_SCAN 3
+#define DV_SCAN 3 /* a shared access that reads the row as DV_RD does (LOCK_SH, storage/row.cpp:191;
+                     the field read, benchmarks/ycsb_txn.cpp:228): counted in read_digest, no range
+                     semantics */
 
 /* index hash (storage/index_hash.h:86-92) */
 #define DV_HASH_YCSB 0 /* (key / part_cnt) % nbuckets */

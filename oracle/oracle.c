@@ -516,8 +516,8 @@ static int epoch_calvin(const uint64_t *keys, const uint64_t *rows, uint64_t *f0
     while (hp.n && !rc) {
         uint32_t t = heap_pop(&hp);
         done++;
-        for (uint64_t a = tb[t]; a < tb[t + 1]; a++)
-            if (types[a] == OR_RD) st->read_digest += read_term(f0[rows[a]], t, keys[a]);
+        for (uint64_t a = tb[t]; a < tb[t + 1]; a++) /* a SCAN reads the field as a RD does (ycsb_txn.cpp:228) */
+            if (types[a] == OR_RD || types[a] == OR_SCAN) st->read_digest += read_term(f0[rows[a]], t, keys[a]);
         for (uint64_t a = tb[t]; a < tb[t + 1]; a++)
             if (types[a] == OR_WR) { f0[rows[a]] = 0; st->write_cnt++; }
         for (uint64_t a = tb[t]; a < tb[t + 1]; a++) {
@@ -592,7 +592,7 @@ static int epoch_2pl(int cc, const uint64_t *keys, const uint64_t *rows, uint64_
         st->committed++;
         for (uint64_t a = tb[t]; a < tb[t + 1]; a++) {
             if (types[a] == OR_WR) st->write_cnt++;
-            else st->read_digest += read_term(rdval[a], t, keys[a]);
+            else st->read_digest += read_term(rdval[a], t, keys[a]); /* RD and SCAN alike (ycsb_txn.cpp:228) */
         }
         for (uint64_t b = tb[t + 1]; b-- > tb[t];)
             if (lock_release(&L, cc, rows[b], t, &dummy_lr, dummy_ready, &nready)) { rc = -3; break; }
@@ -682,7 +682,7 @@ static int epoch_occ(const uint64_t *keys, const uint64_t *rows, uint64_t *f0, u
         st->committed++;
         for (uint64_t a = tb[t]; a < tb[t + 1]; a++) {
             if (types[a] == OR_WR) { f0[rows[a]] = 0; st->write_cnt++; }
-            else st->read_digest += read_term(rdval[a], t, keys[a]);
+            else st->read_digest += read_term(rdval[a], t, keys[a]); /* RD and SCAN alike (ycsb_txn.cpp:228) */
         }
     }
     free(start_ts); free(rdval);

@@ -133,23 +133,39 @@ def structural_constants():
 # NO_WAIT / WAIT_DIE / OCC: T_0 commits, T_1 meets T_0's lock (write) on row 1
 # and aborts, T_2 then finds row 2 free ... T_k commits iff k is even.
 # CALVIN: all commit.  A dependency chain L deep: T_k's verdict needs T_{k-1}'s.
-def ladder(L, empties=False):
+# reads=True: T_k = [W k, W k+1] + 1 + k % 2 reads of private rows (L + 1 on,
+# each read once in the whole epoch).  A private read conflicts with nothing,
+# so every formula stays; the carried txns carry their reads along.
+def _ladder_arrays(k, L, reads):
+    """(lens, keys, types) of ladder txns k, private rows as in the whole ladder"""
+    nr = (1 + k % 2) if reads else np.zeros(len(k), np.int64)
+    priv0 = L + 1 + k + k // 2  # (1 + j % 2 summed over j < k)
+    lens = 2 + nr
+    tb = np.r_[0, np.cumsum(lens)]
+    txn = np.repeat(np.arange(len(k)), lens)
+    j = np.arange(int(tb[-1])) - tb[txn]
+    keys = np.where(j < 2, k[txn] + j, priv0[txn] + j - 2)
+    return lens, keys, (j < 2).astype(np.uint8)
+
+
+def ladder(L, empties=False, reads=False):
     k = np.arange(L, dtype=np.int64)
-    keys = np.stack([k, k + 1], 1).ravel()
-    lens = np.full(L, 2)
+    lens, keys, types = _ladder_arrays(k, L, reads)
     even = (k % 2 == 0).astype(np.uint8)
     if empties:  # family 8: an empty txn after every ladder txn (empties commit)
         lens = np.stack([lens, np.zeros(L, np.int64)], 1).ravel()
         even = np.stack([even, _ones(L)], 1).ravel()
-    e = _mk(lens, keys, _ones(2 * L))
+    e = _mk(lens, keys, types)
     exp = {cc: even.copy() for cc in LOCKING + ("OCC",)}
     exp["CALVIN"] = _ones(e.n_txn)
     # the aborted txns, in order and renumbered from 0: the odd ladder txns,
-    # L // 2 of them with 2 accesses each; they touch disjoint rows (k, k+1
-    # for odd k), so run as the next epoch all of them commit
+    # L // 2 of them with their accesses unchanged; they touch disjoint rows
+    # (k, k+1 for odd k, and private ones), so run as the next epoch all of
+    # them commit
     odd = k[1::2]
-    carried = _mk(np.full(len(odd), 2), np.stack([odd, odd + 1], 1).ravel(), _ones(2 * len(odd)))
-    return Case(e, L + 1, exp, carried=carried)
+    carried = _mk(*_ladder_arrays(odd, L, reads))
+    return Case(e, L + 1 + (int(lens.sum()) - 2 * L if reads else 0), exp, carried=carried,
+                extra=dict(carried_from=odd * (2 if empties else 1)))
 
 
 # ---- family 2: Ladder + hot row(L, f).  Ladder txn k = [X hot, W k, W k+1],
@@ -329,7 +345,10 @@ def width_boundary(n_txn, L=2001):
 # The carried epoch is block 2's txns then the 19 aborting ones of the last,
 # partial block, in order, one write each on distinct rows: run as the next
 # epoch they all commit.
-def carry_blocks(B):
+# reads=True: every txn that is not empty reads a private row after its write
+# (row 2 B + 8 + j for the j-th of them, read once in the whole epoch), which
+# conflicts with nothing; the carried txns carry their reads along.
+def carry_blocks(B, reads=False):
     k = np.arange(B, dtype=np.int64)
     tail_n = 37
     ti = np.arange((tail_n + 1) // 2, dtype=np.int64)
@@ -337,11 +356,22 @@ def carry_blocks(B):
     tl[0::2] = 1
     lens = np.r_[np.zeros(B, np.int64), np.ones(3 * B, np.int64), tl]
     keys = np.r_[k, k, B + k, B + ti]
-    e = _mk(lens, keys, _ones(len(keys)))
-    c = np.r_[_ones(2 * B), np.zeros(B, np.uint8), _ones(B), (tl == 0).astype(np.uint8)]
+    cj = np.r_[B + k, 3 * B + ti]  # the carried txns among the ones that are not empty
     ck = np.r_[k, B + ti]
-    carried = _mk(np.ones(len(ck), np.int64), ck, _ones(len(ck)))
-    return Case(e, 2 * B + 8, {cc: c.copy() for cc in LOCKING + ("OCC",)}, carried=carried)
+    assert np.array_equal(keys[cj], ck)
+    rows = 2 * B + 8
+    types = _ones(len(keys))
+    if reads:
+        priv = rows + np.arange(len(keys), dtype=np.int64)
+        ck = np.stack([ck, priv[cj]], 1).ravel()
+        keys, types, lens = np.stack([keys, priv], 1).ravel(), np.tile(np.uint8([WR, RD]), len(keys)), 2 * lens
+        rows += len(priv)
+    e = _mk(lens, keys, types)
+    c = np.r_[_ones(2 * B), np.zeros(B, np.uint8), _ones(B), (tl == 0).astype(np.uint8)]
+    per = 2 if reads else 1
+    carried = _mk(np.full(len(cj), per), ck, np.tile(types[:per], len(cj)))
+    return Case(e, rows, {cc: c.copy() for cc in LOCKING + ("OCC",)}, carried=carried,
+                extra=dict(carried_from=np.r_[2 * B + k, 4 * B + 2 * ti]))
 
 
 def contiguous_chunks(e, world):

@@ -100,13 +100,13 @@ def serial_model(epoch, f0_before, pkey):
             grant[a] = mine[r]
         for a in range(tb[t], tb[t + 1]):
             r = int(rows[a])
-            if types[a] == RD:
+            if types[a] != WR:  # RD, SCAN
                 values[a] = 0 if (r in written or f0_before[r] == 0) else f0_before[r]
         for a in range(tb[t], tb[t + 1]):
             if types[a] == WR:
                 writes += 1
                 written.add(int(rows[a]))
-    rd = types == RD
+    rd = types != WR
     digest = read_digest(values[rd], e.acc_txn()[rd], e.keys[rd])
     f0 = np.array(f0_before, np.uint64, copy=True)
     f0[sorted(written)] = 0
@@ -119,7 +119,7 @@ def outcome(case, f0_before, pkey=None):
     what its row held"""
     e = case.epoch
     rows = rows_of(e.keys, pkey) if pkey is not None else e.keys.astype(np.int64)
-    rd = e.types == RD
+    rd = e.types != WR  # RD and SCAN: both read the row (ycsb_txn.cpp:228)
     assert not case.sees0[~rd].any()
     values = np.where(case.sees0, np.uint64(0), np.asarray(f0_before, np.uint64)[rows])
     digest = read_digest(values[rd], e.acc_txn()[rd], e.keys[rd])
