@@ -4095,6 +4095,12 @@ static bool wire_tpcc_knobs_ok(const dv_tpcc_params *tp) {
     uint32_t beg;
     return tp && dv_tpcc_expand(tp, nullptr, 0, 0, &k, &ty, &tb, &a, &beg, nullptr, nullptr) == DV_OK;
 }
+// the sequencer's cfg: YCSB, or TPC-C with its knobs, under CALVIN; a txn's participants are one 64-bit mask
+static bool wire_seq_cfg_ok(const dv_wire_cfg *cfg) {
+    return (cfg->workload == DV_YCSB || (cfg->workload == DV_TPCC && wire_tpcc_knobs_ok(cfg->tpcc))) &&
+           cfg->calvin == 1 && cfg->part_cnt && cfg->node_cnt && cfg->node_cnt <= DV_WIRE_SEQ_NODE_MAX &&
+           cfg->node_id < cfg->node_cnt;
+}
 }  // extern "C++"
 
 int dv_wire_ingest_device(dv_ctx *c, const dv_wire_cfg *cfg, const uint8_t *buf, uint64_t buf_len,
@@ -4281,10 +4287,7 @@ int dv_wire_sequence_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wire_seq
     if (!c || !cfg || !in || !out || !res || !in->buf || !in->off) return DV_ERR_ARG;
     if (!out->out || !out->batch_off || !out->dest_first || !out->wait_client || !out->wait_startts || !out->wait_acks)
         return DV_ERR_ARG;
-    // YCSB under CALVIN; a txn's participants are one 64-bit mask
-    if (cfg->workload != DV_YCSB || cfg->calvin != 1 || !cfg->part_cnt || !cfg->node_cnt ||
-        cfg->node_cnt > DV_WIRE_SEQ_NODE_MAX || cfg->node_id >= cfg->node_cnt)
-        return DV_ERR_ARG;
+    if (!wire_seq_cfg_ok(cfg)) return DV_ERR_ARG;
     if (in->batch_id == ~0ull || !in->max_txn || in->max_txn > kSeqMaxTxn || in->first_batch > in->n_batches)
         return DV_ERR_ARG;
     if (in->n_dest < cfg->node_cnt || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
@@ -4311,9 +4314,7 @@ int dv_wire_sequence_acks_device(dv_ctx *c, const dv_wire_cfg *cfg, const dv_wir
     KProfScope kps_(c);
     if (!c || !cfg || !in || !out || !res || !in->buf || !in->off || !out->out || !out->batch_off) return DV_ERR_ARG;
     if (in->n_txn && (!in->wait_client || !in->wait_startts || !in->wait_acks)) return DV_ERR_ARG;
-    if (cfg->workload != DV_YCSB || cfg->calvin != 1 || !cfg->part_cnt || !cfg->node_cnt ||
-        cfg->node_cnt > DV_WIRE_SEQ_NODE_MAX || cfg->node_id >= cfg->node_cnt)
-        return DV_ERR_ARG;
+    if (!wire_seq_cfg_ok(cfg)) return DV_ERR_ARG;
     if (in->batch_id == ~0ull || !in->n_dest || in->n_dest > DV_WIRE_DEST_MAX) return DV_ERR_ARG;
     if (in->n_batches > (1u << 26)) return DV_ERR_ARG;  // (a stream position, 64 to an mbuf, in 32 bits)
     if (reinterpret_cast<uintptr_t>(out->out) & 3u) return DV_ERR_ARG;  // (written in whole dwords)

@@ -1551,6 +1551,46 @@ __device__ __forceinline__ uint32_t seq_next(const uint32_t *s, uint32_t i) {
     return i + k;
 }
 
+// ---- a TPC-C cfg's out: every size is 3 mod 4, so entries (mbuf headers,
+// messages, RDONEs) start at any byte and neighbours share dwords, written by
+// different threads, waves and kernels.  No dword is ever read back: a dword
+// wholly inside one entry is one aligned dword store, the bytes at an entry's
+// two edges are byte stores.  byte_at(k) / dword_at(k): the entry's byte k, its
+// bytes [k, k + 4) -- composed per position in the entry, whatever its start.
+// One thread writes the entry's n bytes at out's byte pos.
+template <class ByteAt>
+__device__ __forceinline__ void seq_put_entry(uint32_t *out, uint64_t pos, uint32_t n, ByteAt byte_at) {
+    uint8_t *out8 = reinterpret_cast<uint8_t *>(out);
+    uint32_t k = 0;
+    for (; k < n && ((pos + k) & 3u); k++) out8[pos + k] = (uint8_t)byte_at(k);
+    for (; k + 4 <= n; k += 4)
+        out[(pos + k) >> 2] = byte_at(k) | byte_at(k + 1) << 8 | byte_at(k + 2) << 16 | byte_at(k + 3) << 24;
+    for (; k < n; k++) out8[pos + k] = (uint8_t)byte_at(k);
+}
+
+// byte k of a stamped header: rtype, txn_id, batch_id, then mq_time and the latencies, zero
+__device__ __forceinline__ uint32_t seq_hdr_byte(uint32_t k, uint32_t rtype, uint64_t id, uint64_t batch_id) {
+    if (k < 4) return (rtype >> (8 * k)) & 0xFFu;
+    if (k < 12) return (uint32_t)(id >> (8 * (k - 4))) & 0xFFu;
+    if (k < 20) return (uint32_t)(batch_id >> (8 * (k - 12))) & 0xFFu;
+    return 0;
+}
+
+// bytes [k, k + 4) of a stamped CL_QRY whose client bytes lie at o of the image
+__device__ __forceinline__ uint32_t seq_msg_dword(const Stage &st, uint32_t o, uint32_t k, uint64_t id,
+                                                  uint64_t batch_id) {
+    if (k >= Seq::kHdr) return st.u32(o + k);
+    if (k >= 20 && k + 4 <= Seq::kHdr) return 0;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint32_t kk = k + j;
+        const uint32_t by = kk < Seq::kHdr ? seq_hdr_byte(kk, DV_WIRE_CL_QRY, id, batch_id) : st.u32(o + kk) & 0xFFu;
+        v |= by << (8 * j);
+    }
+    return v;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(kBlock) void k_seq_check(dv_wire_cfg cfg, uint32_t n_dest,
@@ -1586,6 +1626,97 @@ __global__ __launch_bounds__(kBlock) void k_seq_check(dv_wire_cfg cfg, uint32_t 
     s_sz[wave][lane] = (uint16_t)size;
     __syncthreads();
     const uint64_t mask = parse && !bad && lane < count ? ((uint64_t)s_pm[wave][lane][1] << 32) | s_pm[wave][lane][0] : 0;
+    const uint32_t sends = __shfl(wave_incl_sum((uint32_t)__popcll(mask), lane), 63, 64);
+    if (!w.live) return;
+    keep_batch<Seq>(ws, w, bad, count, my.off, count, sends, count);  // (bm: the mbuf's messages)
+    if (!bad && lane < count) {
+        ws.mmask[(uint64_t)w.b * Seq::kStride + lane] = mask;
+        ws.msz[(uint64_t)w.b * Seq::kStride + lane] = (uint16_t)size;
+    }
+    if (lane < cfg.node_cnt) {  // destination `lane`: its messages and bytes of this mbuf
+        uint32_t c = 0, by = 0;
+        for (uint32_t m = 0; !bad && m < count; m++)
+            if (s_pm[wave][m][lane >> 5] >> (lane & 31u) & 1u) c++, by += s_sz[wave][m];
+        ws.dcnt[(uint64_t)lane * nb + w.b] = c;
+        ws.dbyt[(uint64_t)lane * nb + w.b] = by;
+    }
+}
+
+// The same for a TPC-C cfg: k_wire_check_tpcc's checks over the Seq dialect
+// (a CALVIN-build TPCCClientQueryMessage is 207 + 8 np + 24 n bytes, always
+// 3 mod 4), then TPCCQuery::participants (tpcc_query.cpp:67-90): lane m adds
+// the nodes of message m's w_id and, for a Payment, c_w_id; the mbuf's
+// NewOrder items, one flat range, add their supply warehouses' -- a Payment's
+// items are not in that range, they never add a participant.
+static_assert(Seq::kFixed + kTpccBody + kTpccTail == 207 && 207 >= Seq::kHdr,
+              "the smallest message is no shorter than the RDONE: kSeqReach holds as for YCSB");
+static_assert((kSeqRoom / 207 + 1) <= kSeqReach && kSeqRoom / 207 == 19 && 19 <= kWireMaxMsg,
+              "an mbuf holds at most 19 TPC-C messages");
+// an mbuf's participants: a message of n items names 1 + n nodes at most (a
+// Payment 2 in 207 bytes), so at most (1 + n) / (207 + 24 n) per byte, largest at n = 62
+static_assert((uint64_t)kSeqRoom * (1 + DV_TPCC_MAX_OL) / (207 + 24 * DV_TPCC_MAX_OL) == 151 &&
+                  kSeqRoom * 2 / 207 <= 151 && 151 <= kSeqMbufParts,
+              "wire_seq_list_cap's bound per mbuf holds for TPC-C");
+__global__ __launch_bounds__(kBlock) void k_seq_check_tpcc(dv_wire_cfg cfg, dv_tpcc_params tp, uint32_t n_dest,
+                                                           const uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                           const uint64_t *__restrict__ off, uint32_t first,
+                                                           uint32_t nb, WireSeqWs ws) {
+    __shared__ uint4 s_img[kWireWave][kStageQ];
+    __shared__ uint32_t s_it[kWireWave][64], s_pp[kWireWave][64];  // NewOrder items / partitions before message m
+    __shared__ uint16_t s_mo[kWireWave][64], s_io[kWireWave][64];  // message m's offset, its first item's
+    __shared__ uint32_t s_pm[kWireWave][64][2];                    // message m's participants
+    __shared__ uint16_t s_sz[kWireWave][64];                       // its bytes
+    s_pm[threadIdx.x >> 6][threadIdx.x & 63][0] = 0;
+    s_pm[threadIdx.x >> 6][threadIdx.x & 63][1] = 0;
+    const WaveBatch w = stage_wave_batch(s_img, buf, buf_len, off, first, nb);
+    const Stage &st = w.st;
+    const uint32_t lane = w.lane, wave = w.wave;
+    const bool parse = w.live && !w.bad;
+    bool bad = w.bad;
+    uint32_t count = 0;
+    Msg my{};
+    if (parse) {
+        const uint32_t src = st.u32(4);  // ISCLIENTN(src)
+        bad = !open_header<Seq>(st, cfg, count) || src < cfg.node_cnt || src >= n_dest ||
+              !walk_chain<Seq>(st, w.len, count, lane, my, [&](uint32_t bo, uint32_t &n) -> uint32_t {
+                  return tpcc_body_end(st, w.len, bo, n);
+              });
+    }
+    bool wrong = false;
+    uint32_t my_acc = 0, my_it = 0;
+    if (parse && !bad && lane < count) wrong = tpcc_fields_wrong(st, tp, my.bo, my.n, my_acc, my_it);
+    // (a bad mbuf's lanes hold zeros or a part of the chain: its tables are not read)
+    const uint32_t it_in = wave_incl_sum(my_it, lane), pp_in = wave_incl_sum(my.np, lane);
+    const uint32_t tot_it = __shfl(it_in, 63, 64), tot_pp = __shfl(pp_in, 63, 64);
+    s_it[wave][lane] = it_in - my_it;
+    s_pp[wave][lane] = pp_in - my.np;
+    s_mo[wave][lane] = (uint16_t)my.off;
+    s_io[wave][lane] = (uint16_t)(my.bo + kTpccBody);
+    __syncthreads();
+    if (parse && !bad) {
+        wrong |= parts_wrong<Seq>(st, s_pp[wave], s_mo[wave], tot_pp, cfg.part_cnt, lane);
+        wrong |= tpcc_items_wrong(st, tp, s_it[wave], s_io[wave], tot_it, lane);
+    }
+    bad = bad || __any(wrong);
+    const bool good = parse && !bad;
+    if (good) {  // (checked: every warehouse is in [1, num_wh], a 32-bit value)
+        const auto add = [&](uint32_t m, uint32_t wh) {
+            const uint32_t node = ((wh - 1) % tp.part_cnt) % cfg.node_cnt;
+            atomicOr(&s_pm[wave][m][node >> 5], 1u << (node & 31u));
+        };
+        if (lane < count) {
+            add(lane, st.u32(my.bo + 8));
+            if (st.u32(my.bo) == 1) add(lane, st.u32(my.bo + 40));
+        }
+        for (uint32_t q = lane; q < tot_it; q += 64) {
+            const uint32_t m = last_le64(s_it[wave], q);
+            add(m, st.u32(s_io[wave][m] + (q - s_it[wave][m]) * kItemBytes + 8u));
+        }
+    }
+    const uint32_t size = good && lane < count ? my.bo + kTpccBody + my.n * kItemBytes + kTpccTail - my.off : 0u;
+    s_sz[wave][lane] = (uint16_t)size;
+    __syncthreads();
+    const uint64_t mask = good && lane < count ? ((uint64_t)s_pm[wave][lane][1] << 32) | s_pm[wave][lane][0] : 0;
     const uint32_t sends = __shfl(wave_incl_sum((uint32_t)__popcll(mask), lane), 63, 64);
     if (!w.live) return;
     keep_batch<Seq>(ws, w, bad, count, my.off, count, sends, count);  // (bm: the mbuf's messages)
@@ -1737,11 +1868,12 @@ __global__ __launch_bounds__(64) void k_seq_plan2(WireSeqWs ws, uint32_t nodes, 
 }
 
 // the tiles again: the starts reachable from where the walk enters the tile,
-// every entry's byte in out, the mbufs' headers and offsets, the RDONE
-__global__ __launch_bounds__(kBlock) void k_seq_marks(WireSeqWs ws, uint32_t nodes, uint32_t ntile, uint32_t node_id,
-                                                      uint64_t batch_id, uint32_t *__restrict__ out,
-                                                      uint64_t *__restrict__ batch_off,
-                                                      uint32_t *__restrict__ dest_first) {
+// every entry's byte in out, the mbufs' headers and offsets, the RDONE.
+// kBytes: a TPC-C cfg's byte-granular out (seq_put_entry); YCSB's whole dwords otherwise.
+template <bool kBytes>
+__device__ __forceinline__ void seq_marks(const WireSeqWs &ws, uint32_t nodes, uint32_t ntile, uint32_t node_id,
+                                          uint64_t batch_id, uint32_t *__restrict__ out,
+                                          uint64_t *__restrict__ batch_off, uint32_t *__restrict__ dest_first) {
     __shared__ uint32_t s_S[kSeqTile + kSeqReach], s_mark[kSeqTile], lds4[4];
     __shared__ uint16_t s_lv[8][kSeqTile];  // level k: 2^k steps along next, kSeqTile: out of the tile
     if (ws.plan->refused) return;
@@ -1773,17 +1905,28 @@ __global__ __launch_bounds__(kBlock) void k_seq_marks(WireSeqWs ws, uint32_t nod
         const uint64_t pos = ws.dDB[d] + (uint64_t)DV_WIRE_HDR * (j + 1) + s_S[i], q = pos >> 2;
         ws.lpos[lb + r] = pos;
         if (start && j < ws.dmb[d]) {  // (always: the chain counted the same starts)
-            out[q - 3] = d;
-            out[q - 2] = node_id;
-            out[q - 1] = nxt - i;
+            if constexpr (kBytes) {
+                const uint32_t h[3] = {d, node_id, nxt - i};
+                seq_put_entry(out, pos - DV_WIRE_HDR, DV_WIRE_HDR,
+                              [&](uint32_t k) { return (h[k >> 2] >> (8 * (k & 3u))) & 0xFFu; });
+            } else {
+                out[q - 3] = d;
+                out[q - 2] = node_id;
+                out[q - 1] = nxt - i;
+            }
             batch_off[ws.dMB[d] + j] = pos - DV_WIRE_HDR;
         }
         if (r == tot && pos + Seq::kHdr <= ws.sres->n_bytes) {  // the RDONE: the header alone (the bound: always)
-            out[q] = DV_WIRE_RDONE;
-            out[q + 1] = out[q + 2] = 0xFFFFFFFFu;
-            out[q + 3] = (uint32_t)batch_id;
-            out[q + 4] = (uint32_t)(batch_id >> 32);
-            for (uint32_t f = 5; f < kSeqHdrDw; f++) out[q + f] = 0;
+            if constexpr (kBytes) {
+                seq_put_entry(out, pos, Seq::kHdr,
+                              [&](uint32_t k) { return seq_hdr_byte(k, DV_WIRE_RDONE, kNoBatchId, batch_id); });
+            } else {
+                out[q] = DV_WIRE_RDONE;
+                out[q + 1] = out[q + 2] = 0xFFFFFFFFu;
+                out[q + 3] = (uint32_t)batch_id;
+                out[q + 4] = (uint32_t)(batch_id >> 32);
+                for (uint32_t f = 5; f < kSeqHdrDw; f++) out[q + f] = 0;
+            }
         }
     }
     if (blockIdx.x == 0 && i == 0) {
@@ -1795,13 +1938,29 @@ __global__ __launch_bounds__(kBlock) void k_seq_marks(WireSeqWs ws, uint32_t nod
     }
 }
 
-// the taken mbufs, a wave each: the wait list, and every message once per participant
-__global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
-                                                     const uint64_t *__restrict__ off, uint32_t first, uint32_t nb,
-                                                     uint64_t batch_id, WireSeqWs ws, uint32_t *__restrict__ out,
-                                                     uint32_t *__restrict__ wait_client,
-                                                     uint64_t *__restrict__ wait_startts,
-                                                     uint32_t *__restrict__ wait_acks) {
+__global__ __launch_bounds__(kBlock) void k_seq_marks(WireSeqWs ws, uint32_t nodes, uint32_t ntile, uint32_t node_id,
+                                                      uint64_t batch_id, uint32_t *__restrict__ out,
+                                                      uint64_t *__restrict__ batch_off,
+                                                      uint32_t *__restrict__ dest_first) {
+    seq_marks<false>(ws, nodes, ntile, node_id, batch_id, out, batch_off, dest_first);
+}
+__global__ __launch_bounds__(kBlock) void k_seq_marks_bytes(WireSeqWs ws, uint32_t nodes, uint32_t ntile,
+                                                            uint32_t node_id, uint64_t batch_id,
+                                                            uint32_t *__restrict__ out,
+                                                            uint64_t *__restrict__ batch_off,
+                                                            uint32_t *__restrict__ dest_first) {
+    seq_marks<true>(ws, nodes, ntile, node_id, batch_id, out, batch_off, dest_first);
+}
+
+// the taken mbufs, a wave each: the wait list, and every message once per participant.
+// kBytes: a message starts at any byte of out -- lanes 0..2 its bytes up to the
+// first aligned dword and behind the last, consecutive lanes the dwords between.
+template <bool kBytes>
+__device__ __forceinline__ void seq_emit(const dv_wire_cfg &cfg, const uint8_t *__restrict__ buf,
+                                         const uint64_t *__restrict__ off, uint32_t first, uint32_t nb,
+                                         uint64_t batch_id, const WireSeqWs &ws, uint32_t *__restrict__ out,
+                                         uint32_t *__restrict__ wait_client, uint64_t *__restrict__ wait_startts,
+                                         uint32_t *__restrict__ wait_acks) {
     __shared__ uint4 s_img[kWireWave][kStageQ];
     const uint32_t taken = ws.plan->taken;
     if (ws.plan->refused || blockIdx.x * kWireWave >= taken) return;
@@ -1811,7 +1970,8 @@ __global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint
     const uint32_t lb = seq_list_base(ws.dtot, cfg.node_cnt, lane);
     if (!w.live) return;
     const uint32_t b = w.b, count = ws.bm[b], t0 = ws.ct[b / kWireChunk] + ws.bt[b];
-    const uint64_t end = ws.sres->n_bytes >> 2;  // (no store at or past it, whatever the words above hold)
+    const uint64_t n_bytes = ws.sres->n_bytes;
+    const uint64_t end = n_bytes >> 2;  // (no store at or past it, whatever the words above hold)
     uint64_t mask = 0;
     uint32_t size = 0, mo = 0;
     if (lane < count) {
@@ -1831,9 +1991,23 @@ __global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint
         while (bal) {  // the messages to d, one after the other: consecutive lanes, consecutive dwords
             const uint32_t m = (uint32_t)__builtin_ctzll(bal);
             bal &= bal - 1;
+            const uint64_t id = worker_txn_id(cfg, t0 + m);
+            if constexpr (kBytes) {
+                const uint64_t p = shfl_u64(pos, m);
+                const uint32_t o = __shfl(mo, (int)m, 64), sz = __shfl(size, (int)m, 64);
+                const uint32_t head = (4u - (uint32_t)(p & 3u)) & 3u, ndw = (sz - head) >> 2;  // (sz >= 207)
+                const uint32_t tail0 = head + 4u * ndw;
+                uint8_t *out8 = reinterpret_cast<uint8_t *>(out);
+                if (lane < head && p + lane < n_bytes)
+                    out8[p + lane] = (uint8_t)seq_msg_dword(st, o, lane, id, batch_id);
+                if (tail0 + lane < sz && p + tail0 + lane < n_bytes)
+                    out8[p + tail0 + lane] = (uint8_t)seq_msg_dword(st, o, tail0 + lane, id, batch_id);
+                for (uint32_t f = lane; f < ndw && p + head + 4u * f + 4u <= n_bytes; f += 64)
+                    out[(p + head + 4u * f) >> 2] = seq_msg_dword(st, o, head + 4u * f, id, batch_id);
+                continue;
+            }
             const uint64_t q = shfl_u64(pos, m) >> 2;
             const uint32_t o = __shfl(mo, (int)m, 64), ndw = __shfl(size, (int)m, 64) >> 2;
-            const uint64_t id = worker_txn_id(cfg, t0 + m);
             for (uint32_t f = lane; f < ndw && q + f < end; f += 64) {
                 uint32_t v = 0;  // mq_time, the latencies
                 if (f == 0) v = DV_WIRE_CL_QRY;
@@ -1846,13 +2020,36 @@ __global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint
     }
 }
 
+__global__ __launch_bounds__(kBlock) void k_seq_emit(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
+                                                     const uint64_t *__restrict__ off, uint32_t first, uint32_t nb,
+                                                     uint64_t batch_id, WireSeqWs ws, uint32_t *__restrict__ out,
+                                                     uint32_t *__restrict__ wait_client,
+                                                     uint64_t *__restrict__ wait_startts,
+                                                     uint32_t *__restrict__ wait_acks) {
+    seq_emit<false>(cfg, buf, off, first, nb, batch_id, ws, out, wait_client, wait_startts, wait_acks);
+}
+__global__ __launch_bounds__(kBlock) void k_seq_emit_bytes(dv_wire_cfg cfg, const uint8_t *__restrict__ buf,
+                                                           const uint64_t *__restrict__ off, uint32_t first,
+                                                           uint32_t nb, uint64_t batch_id, WireSeqWs ws,
+                                                           uint32_t *__restrict__ out,
+                                                           uint32_t *__restrict__ wait_client,
+                                                           uint64_t *__restrict__ wait_startts,
+                                                           uint32_t *__restrict__ wait_acks) {
+    seq_emit<true>(cfg, buf, off, first, nb, batch_id, ws, out, wait_client, wait_startts, wait_acks);
+}
+
 void launch_seq_plan(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in &in, const dv_wire_seq_out &out,
                      uint32_t nb, const WireSeqWs &ws) {
     const uint32_t nc = (nb + kWireChunk - 1) / kWireChunk, nodes = cfg.node_cnt, nbn = nb ? nb : 1;
     const uint32_t ntile = wire_seq_tiles(nbn, in.max_txn), grid = (nb + kWireWave - 1) / kWireWave;
     (void)hipMemsetAsync(ws.first, 0xFF, 2 * sizeof(uint32_t), s);  // kNoBatch
     if (nb) {
-        DV_LAUNCH(k_seq_check, grid, kBlock, 0, s, cfg, in.n_dest, in.buf, in.buf_len, in.off, in.first_batch, nb, ws);
+        if (cfg.workload == DV_TPCC)
+            DV_LAUNCH(k_seq_check_tpcc, grid, kBlock, 0, s, without_tpcc(cfg), *cfg.tpcc, in.n_dest, in.buf, in.buf_len,
+                      in.off, in.first_batch, nb, ws);
+        else
+            DV_LAUNCH(k_seq_check, grid, kBlock, 0, s, cfg, in.n_dest, in.buf, in.buf_len, in.off, in.first_batch, nb,
+                      ws);
         DV_LAUNCH(k_wire_scan, nc, kBlock, 0, s, ws, nb);
     }
     DV_LAUNCH(k_seq_plan, 1, kBlock, 0, s, ws, in.first_batch, nb, in.n_batches, nc, in.max_txn);
@@ -1867,11 +2064,20 @@ void launch_seq_emit(hipStream_t s, const dv_wire_cfg &cfg, const dv_wire_seq_in
                      uint32_t nb, const WireSeqWs &ws) {
     const uint32_t nodes = cfg.node_cnt, nbn = nb ? nb : 1, ntile = wire_seq_tiles(nbn, in.max_txn);
     uint32_t *out32 = reinterpret_cast<uint32_t *>(out.out);
+    const uint32_t grid = (nb + kWireWave - 1) / kWireWave;
+    if (cfg.workload == DV_TPCC) {  // sizes 3 mod 4: entries at any byte
+        DV_LAUNCH(k_seq_marks_bytes, dim3(ntile, nodes), kBlock, 0, s, ws, nodes, ntile, cfg.node_id, in.batch_id, out32,
+                  out.batch_off, out.dest_first);
+        if (nb)
+            DV_LAUNCH(k_seq_emit_bytes, grid, kBlock, 0, s, without_tpcc(cfg), in.buf, in.off, in.first_batch, nbn,
+                      in.batch_id, ws, out32, out.wait_client, out.wait_startts, out.wait_acks);
+        return;
+    }
     DV_LAUNCH(k_seq_marks, dim3(ntile, nodes), kBlock, 0, s, ws, nodes, ntile, cfg.node_id, in.batch_id, out32,
               out.batch_off, out.dest_first);
     if (nb)
-        DV_LAUNCH(k_seq_emit, (nb + kWireWave - 1) / kWireWave, kBlock, 0, s, cfg, in.buf, in.off, in.first_batch, nbn,
-                  in.batch_id, ws, out32, out.wait_client, out.wait_startts, out.wait_acks);
+        DV_LAUNCH(k_seq_emit, grid, kBlock, 0, s, cfg, in.buf, in.off, in.first_batch, nbn, in.batch_id, ws,
+                  out32, out.wait_client, out.wait_startts, out.wait_acks);
 }
 
 // ---- the sequencer's acks in (dv_wire_sequence_acks_device): what

@@ -161,6 +161,14 @@ extern "C" int dv_wire_epoch_reset(dv_wire_epoch *ep) {
 }
 
 namespace {
+// a parsed TPC-C query's fields as the access-list expansion checks them (into scratch arrays)
+bool tpcc_fields_ok(const dv_wire_cfg *c, const Msg &m) {
+    uint64_t k[3 + 2 * DV_TPCC_MAX_OL], a[3 + 2 * DV_TPCC_MAX_OL];
+    uint8_t ty[3 + 2 * DV_TPCC_MAX_OL], tb[3 + 2 * DV_TPCC_MAX_OL];
+    uint32_t beg[2];
+    return dv_tpcc_expand(c->tpcc, &m.tq, 1, 3 + 2 * DV_TPCC_MAX_OL, k, ty, tb, a, beg, nullptr, nullptr) == DV_OK;
+}
+
 // one message at r: header, client part and body, every field checked (the
 // TPC-C ones by the access-list expansion into scratch arrays) -- or, for a
 // batch dv_wire_open has checked (check false), only parsed
@@ -170,11 +178,7 @@ bool read_msg(const dv_wire_cfg *c, Reader &r, Msg &m, bool check = true) {
     if (m.rtype == DV_WIRE_RDONE) return true;
     if (c->workload != DV_TPCC) return read_ycsb(c, r, m, check);
     if (!read_tpcc(r, m)) return false;
-    if (!check) return true;
-    uint64_t k[3 + 2 * DV_TPCC_MAX_OL], a[3 + 2 * DV_TPCC_MAX_OL];
-    uint8_t ty[3 + 2 * DV_TPCC_MAX_OL], tb[3 + 2 * DV_TPCC_MAX_OL];
-    uint32_t beg[2];
-    return dv_tpcc_expand(c->tpcc, &m.tq, 1, 3 + 2 * DV_TPCC_MAX_OL, k, ty, tb, a, beg, nullptr, nullptr) == DV_OK;
+    return !check || tpcc_fields_ok(c, m);
 }
 
 bool cfg_ok(const dv_wire_cfg *c) {
@@ -335,9 +339,17 @@ constexpr uint64_t kAckBytes = 88;        // AckMessage: header + RC
 constexpr uint64_t kSeqRspBytes = 92;     // ClientResponseMessage: header + client_startts
 constexpr uint32_t kAckPer = (DV_WIRE_MSG_MAX - DV_WIRE_HDR) / kAckBytes;  // 46
 
+// the knobs themselves, as the expansion of no query checks them
+bool tpcc_knobs_ok(const dv_tpcc_params *tp) {
+    uint64_t k, a;
+    uint8_t ty, tb;
+    uint32_t beg;
+    return tp && dv_tpcc_expand(tp, nullptr, 0, 0, &k, &ty, &tb, &a, &beg, nullptr, nullptr) == DV_OK;
+}
+
 bool seq_cfg_ok(const dv_wire_cfg *c) {
-    return c && c->workload == DV_YCSB && c->calvin == 1 && c->part_cnt && c->node_cnt &&
-           c->node_cnt <= DV_WIRE_SEQ_NODE_MAX && c->node_id < c->node_cnt;
+    return c && (c->workload == DV_YCSB || (c->workload == DV_TPCC && tpcc_knobs_ok(c->tpcc))) && c->calvin == 1 &&
+           c->part_cnt && c->node_cnt && c->node_cnt <= DV_WIRE_SEQ_NODE_MAX && c->node_id < c->node_cnt;
 }
 
 // mbuf b of the queue: its bytes, false where off decreases, points past the
@@ -368,17 +380,29 @@ bool seq_client_mbuf(const dv_wire_cfg *cfg, uint32_t n_dest, const uint8_t *p, 
         Msg m;
         const uint8_t *at = r.p;
         // (the message's own txn_id and batch_id are not looked at: a client sends UINT64_MAX in both)
-        const bool ok = read_client_part(cfg, r, m, true) && m.rtype == DV_WIRE_CL_QRY && read_ycsb(cfg, r, m, true) &&
-                        m.n_acc > 0;
+        bool ok = read_client_part(cfg, r, m, true) && m.rtype == DV_WIRE_CL_QRY;
+        if (ok && cfg->workload == DV_TPCC)
+            ok = read_tpcc(r, m) && tpcc_fields_ok(cfg, m);
+        else if (ok)
+            ok = read_ycsb(cfg, r, m, true) && m.n_acc > 0;
         if (!ok) {
             txns.resize(keep);
             return false;
         }
-        uint64_t parts = 0;  // YCSBQuery::participants: GET_NODE_ID(key_to_part(key))
-        for (uint32_t q = 0; q < m.n_acc; q++) {
-            uint64_t key;
-            std::memcpy(&key, m.reqs + q * kYcsbReq + 8, 8);
-            parts |= 1ull << ((key % cfg->part_cnt) % cfg->node_cnt);
+        uint64_t parts = 0;
+        if (cfg->workload == DV_TPCC) {
+            // TPCCQuery::participants: GET_NODE_ID(wh_to_part(w)) of w_id and, for a Payment, c_w_id, for a
+            // NewOrder, its items' supply warehouses (read_tpcc: a Payment's ol_cnt is 0, its items never count)
+            const auto node = [&](uint64_t w) { return ((w - 1) % cfg->tpcc->part_cnt) % cfg->node_cnt; };
+            parts |= 1ull << node(m.tq.w_id);
+            if (m.tq.txn_type == 1) parts |= 1ull << node(m.tq.c_w_id);
+            for (uint64_t q = 0; q < m.tq.ol_cnt; q++) parts |= 1ull << node(m.tq.items[q].ol_supply_w_id);
+        } else {  // YCSBQuery::participants: GET_NODE_ID(key_to_part(key))
+            for (uint32_t q = 0; q < m.n_acc; q++) {
+                uint64_t key;
+                std::memcpy(&key, m.reqs + q * kYcsbReq + 8, 8);
+                parts |= 1ull << ((key % cfg->part_cnt) % cfg->node_cnt);
+            }
         }
         txns.push_back(SeqTxn{at, (uint32_t)(r.p - at), h[1], m.client_startts, parts});
     }

@@ -604,8 +604,12 @@ class CalvinTpccDeviceWireIngress(_CalvinStreams):
         return ep
 
 
-def _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req):
-    return L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
+def _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req, params=None):
+    """the sequencer's cfg: YCSB, or TPC-C following `params` (a TpccParams,
+    which the caller keeps alive as long as the cfg points at it)"""
+    if params is None:
+        return L.WireCfg(L.YCSB, 1, node_id, node_cnt, part_cnt, max_req, synth_table_size, None)
+    return L.WireCfg(L.TPCC, 1, node_id, node_cnt, part_cnt, 0, 0, ctypes.pointer(params))
 
 
 def _seq_room(in_bytes, node_cnt):
@@ -646,18 +650,19 @@ class SequencedBatch:
         return [self.out[int(self.batch_off[j]):int(self.batch_off[j + 1])].tobytes() for j in range(lo, hi)]
 
 
-def sequence_host(buf, off, batch_id, *, node_id, node_cnt, part_cnt, synth_table_size, n_dest, max_txn, max_req=0,
-                  first_batch=0, cap=None, max_batches=None):
+def sequence_host(buf, off, batch_id, *, node_id, node_cnt, part_cnt, synth_table_size=0, n_dest, max_txn, max_req=0,
+                  first_batch=0, cap=None, max_batches=None, params=None):
     """dv_wire_sequence over numpy arrays: the client mbufs first_batch.. of
     buf (uint8) at offsets off (u64 [n + 1]) stamped as batch batch_id of
     sequencer node_id and fanned out -> SequencedBatch.  cap / max_batches
-    default to what the input cannot pass.  A call the library refuses before
+    default to what the input cannot pass.  With `params` (a TpccParams) the
+    mbufs are TPC-C's, YCSB's otherwise.  A call the library refuses before
     it looks at the bytes raises; result.status holds every other outcome."""
     buf, off = np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(off, np.uint64)
     blen = len(buf)
     if not blen:
         buf = np.zeros(1, np.uint8)  # (an empty queue still has an address)
-    cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req)
+    cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req, params)  # (params: alive to the return)
     room = _seq_room(blen, node_cnt)
     cap, max_b = room[0] if cap is None else cap, room[1] if max_batches is None else max_batches
     b = SequencedBatch(np.zeros(max(cap, 4), np.uint8), np.zeros(max_b + 1, np.uint64),
@@ -674,11 +679,12 @@ def sequence_host(buf, off, batch_id, *, node_id, node_cnt, part_cnt, synth_tabl
 
 
 def sequence_acks_host(buf, off, batch_id, wait_client, wait_startts, wait_acks, *, node_id, node_cnt, n_dest,
-                       part_cnt=1, cap=None, max_batches=None):
+                       part_cnt=1, cap=None, max_batches=None, params=None):
     """dv_wire_sequence_acks over numpy arrays: the ack mbufs of buf / off
     counted against batch batch_id's wait list (wait_acks, uint32, is updated
     in place) -> (out, batch_off, result), the CL_RSP mbufs of the txns that
-    completed at out[batch_off[j]:batch_off[j + 1]], j < result.n_batches."""
+    completed at out[batch_off[j]:batch_off[j + 1]], j < result.n_batches.
+    With `params` (a TpccParams) the cfg is TPC-C's; the acks are the same."""
     buf, off = np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(off, np.uint64)
     blen = len(buf)
     if not blen:
@@ -686,7 +692,7 @@ def sequence_acks_host(buf, off, batch_id, wait_client, wait_startts, wait_acks,
     assert wait_acks.dtype == np.uint32 and wait_acks.flags.c_contiguous
     wc, ws = np.ascontiguousarray(wait_client, np.uint32), np.ascontiguousarray(wait_startts, np.uint64)
     n = len(wait_acks)
-    cfg = _seq_cfg(node_id, node_cnt, part_cnt, 0, 0)
+    cfg = _seq_cfg(node_id, node_cnt, part_cnt, 0, 0, params)
     room = _seq_rsp_room(n, n_dest)
     cap, max_b = room[0] if cap is None else cap, room[1] if max_batches is None else max_batches
     out, boff = np.zeros(max(cap, 4), np.uint8), np.zeros(max_b + 1, np.uint64)
@@ -702,7 +708,8 @@ def sequence_acks_host(buf, off, batch_id, wait_client, wait_startts, wait_acks,
 
 class DeviceSequencer:
     """The CALVIN sequencer of node node_id on `engine`'s context and stream
-    (dv_wire_sequence_device / dv_wire_sequence_acks_device, YCSB).  It owns
+    (dv_wire_sequence_device / dv_wire_sequence_acks_device): YCSB client
+    mbufs, or TPC-C's following `params` (a TpccParams) when given.  It owns
     the wait list of the batch it sequenced last (wait_client, wait_startts,
     wait_acks: device tensors of max_txn entries, n_txn of them live) and the
     output tensors, which the next call of the same kind overwrites.  cap /
@@ -710,10 +717,11 @@ class DeviceSequencer:
     they are what the call's input cannot pass."""
 
     def __init__(self, engine, node_id, node_cnt, part_cnt, synth_table_size, max_req, max_txn, n_dest, cap=None,
-                 max_batches=None, device="cuda"):
+                 max_batches=None, device="cuda", params=None):
         import torch
         self.engine, self._dev = engine, device
-        self.cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req)
+        self.params = params  # (the cfg points at it)
+        self.cfg = _seq_cfg(node_id, node_cnt, part_cnt, synth_table_size, max_req, params)
         self.node_id, self.node_cnt, self.n_dest, self.max_txn = node_id, node_cnt, n_dest, int(max_txn)
         self.cap, self.max_batches = cap, max_batches
         new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=device)  # noqa: E731

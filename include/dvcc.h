@@ -68,7 +68,7 @@
  *   dv_wire_respond_device      dv_wire_respond's mbufs packed on the device from reply
  *                               fields in device memory (same reference lines)
  *   dv_wire_sequence[_device] / a CALVIN sequencer's own role (system/sequencer.cpp:55-326,
- *   dv_wire_sequence_acks[_device] YCSB): client CL_QRYs stamped, fanned out per participant
+ *   dv_wire_sequence_acks[_device] YCSB and TPC-C): client CL_QRYs stamped, fanned out per participant
  *                               and closed with RDONEs; CALVIN_ACKs counted, CL_RSPs sent
  *
  * Decisions follow SURVEY.md 8.0 ("E-schedule"): commit/abort of every txn and
@@ -1571,8 +1571,9 @@ int dv_wire_respond_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_rs
  * dv_wire_sequence stamps one batch of client CL_QRYs and fans it out
  * (Sequencer::process_txn / send_next_batch, sequencer.cpp:184-326);
  * dv_wire_sequence_acks counts the servers' CALVIN_ACKs against the batch's
- * wait list and answers the clients (Sequencer::process_ack, 55-181).  YCSB
- * only: cfg->workload == DV_YCSB, cfg->calvin == 1, cfg->node_id <
+ * wait list and answers the clients (Sequencer::process_ack, 55-181).  Both
+ * workloads: cfg->workload == DV_YCSB, or DV_TPCC with cfg->tpcc set (knobs
+ * that dv_tpcc_expand accepts); cfg->calvin == 1, cfg->node_id <
  * cfg->node_cnt <= DV_WIRE_SEQ_NODE_MAX (a txn's participants are one 64-bit
  * mask).  The host functions take host pointers, the device functions device
  * pointers (wait list included); the device functions write what the host
@@ -1632,13 +1633,31 @@ typedef struct dv_wire_seq_result {
  * packed as MessageThread::run packs: a 12-byte header {d, node_id, count}, a
  * message that would pass 4,096 bytes opens the next mbuf.  A batch without a
  * txn is node_cnt mbufs of one RDONE.
+ * A TPC-C cfg (cfg->workload == DV_TPCC, cfg->tpcc set) changes two things, the
+ * body check and the participants; everything else above holds as it stands.
+ *  - Every message is a CL_QRY with what dv_wire_open checks of a TPC-C CL_QRY
+ *    under a CALVIN cfg: its partitions below cfg->part_cnt, at most
+ *    DV_TPCC_MAX_PARTS; at most DV_TPCC_MAX_OL items; txn type 1 or 2; w_id,
+ *    d_id (a Payment's c_w_id, c_d_id) inside the tables; a NewOrder's c_id in
+ *    range, ol_cnt == its item count >= 1 and every item's id, supply warehouse
+ *    and quantity in range; a Payment's items skipped unchecked, its c_id in
+ *    range or, by name, a NUL in c_last; operands within 56 bits.  The same
+ *    rule as dv_wire_open's, not a second one.
+ *  - P_k (TPCCQuery::participants, benchmarks/tpcc_query.cpp:67-90), with
+ *    node(w) = ((w - 1) % cfg->tpcc->part_cnt) % node_cnt (wh_to_part as
+ *    dv_tpcc_expand computes the owner, then GET_NODE_ID): a Payment's is
+ *    {node(w_id), node(c_w_id)}, a NewOrder's {node(w_id)} and node(
+ *    ol_supply_w_id) of its ol_cnt items.  A Payment's leftover items add none.
+ *  - A CALVIN build's TPCCClientQueryMessage is 207 + 8 np + 24 n bytes, always
+ *    3 mod 4: out stays 4-byte aligned at its start and the mbufs back to back,
+ *    so batch_off[j], and every message and RDONE, may lie at any byte.
  * Bytes against cap and mbufs against max_batches are decided before anything
  * is written: such a call is DV_ERR_ARG, writes no byte of out, batch_off,
  * dest_first or the wait list, and n_out / n_bytes hold what it needed
  * (n_taken, n_txn, n_msgs what it would have taken).  Nothing is written at or
  * past out[n_bytes], batch_off[n_out + 1] or wait-list entry n_txn.
  * Refused with DV_ERR_ARG and *res untouched: a null pointer, another workload,
- * calvin == 0, part_cnt == 0, node_id >= node_cnt, node_cnt >
+ * DV_TPCC without cfg->tpcc (or with knobs dv_tpcc_expand refuses), calvin == 0, part_cnt == 0, node_id >= node_cnt, node_cnt >
  * DV_WIRE_SEQ_NODE_MAX, n_dest < node_cnt or > DV_WIRE_DEST_MAX, batch_id
  * UINT64_MAX, max_txn == 0, first_batch > n_batches, out not 4-byte aligned.
  * The device call is queued on the context's stream and waits for the result
@@ -1690,7 +1709,9 @@ typedef struct dv_wire_seq_ack_result {
  * full mbuf) to wait_client[k]: txn_id = node_id + node_cnt * k, batch_id
  * UINT64_MAX, client_startts = wait_startts[k].  Packed as
  * dv_wire_respond_device packs: destinations ascending, a destination's
- * replies in that order; out, batch_off, cap and max_batches as there. */
+ * replies in that order; out, batch_off, cap and max_batches as there.  The
+ * acks and the replies do not depend on the workload: a TPC-C cfg (with
+ * cfg->tpcc set, refused without) behaves exactly as a YCSB one. */
 int dv_wire_sequence_acks(const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in, const dv_wire_rsp_out *out,
                           dv_wire_seq_ack_result *res);
 int dv_wire_sequence_acks_device(dv_ctx *ctx, const dv_wire_cfg *cfg, const dv_wire_seq_ack_in *in,

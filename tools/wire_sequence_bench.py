@@ -15,8 +15,13 @@ Shapes (--shape): ten-request YCSB txns, theta 0.6, from four clients
   b    config B's CALVIN batch: 65,536 txns, one node
   b4   the same over 4 nodes at part_cnt 4
   m8   1,048,576 txns over 8 nodes at part_cnt 8
+With --workload tpcc: dv_tpcc_gen_queries' queries (config E's knobs, 32
+warehouses, one partition per node) encoded here as the clients' CL_QRYs of a
+CALVIN build (tests/wire_fmt.tpcc_query), shapes b and b4.  A TPC-C message is
+3 mod 4 bytes: the emit and the marks are the byte-granular kernels
+(k_seq_emit_bytes, k_seq_marks_bytes).
 
-    python tools/wire_sequence_bench.py --shape b|b4|m8 [--reps R] [--iters K] [--out FILE]
+    python tools/wire_sequence_bench.py --shape b|b4|m8 [--workload ycsb|tpcc] [--reps R] [--iters K] [--out FILE]
 """
 import argparse
 import ctypes
@@ -34,13 +39,18 @@ sys.path.insert(0, os.path.join(ROOT, "deneva-plus_amd"))
 import dvcc  # noqa: E402
 from dvcc import _lib as L  # noqa: E402
 from dvcc import wire as DW  # noqa: E402
+from dvcc.tpcc import tpcc_params  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shape", choices=["b", "b4", "m8"], required=True)
+ap.add_argument("--workload", choices=["ycsb", "tpcc"], default="ycsb")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+tpcc = args.workload == "tpcc"
+if tpcc and args.shape == "m8":
+    ap.error("--workload tpcc has the shapes b and b4")
 
 n, nodes = {"b": (65_536, 1), "b4": (65_536, 4), "m8": (1_048_576, 8)}[args.shape]
 part_cnt, rows, R, NODE, E = nodes, 16_777_216, 10, 0, 4
@@ -51,39 +61,68 @@ def sync():
     torch.cuda.synchronize()
 
 
-# ---- the receive queue: the clients' mbufs of a CALVIN build (84-byte header), numpy all the way
-gen = dvcc.YCSBQueryGenerator(rows, part_cnt=part_cnt, req_per_query=R, zipf_theta=0.6, txn_write_perc=1.0,
-                              tup_write_perc=0.5, part_per_txn=min(part_cnt, 2), strict_ppt=0, mpr=-1.0)
-ep = gen.gen(n, dvcc.epoch_seed(0, 7))
-assert (np.diff(ep.txn_begin.astype(np.int64)) == R).all()
-req = np.dtype([("acc", "<u4"), ("pad", "<u4"), ("key", "<u8"), ("val", "u1"), ("pad2", "u1", (7,))])
-# (every query names one partition here, whatever its keys: the sequencer routes by the keys, the list is only checked)
-msg = np.dtype([("rtype", "<u4"), ("txn_id", "<u8"), ("batch_id", "<u8"), ("mq", "<u8"), ("lat", "<f8", (7,)),
-                ("cst", "<u8"), ("np", "<u8"), ("part", "<u8"), ("nreq", "<u8"), ("req", req, (R,))], align=False)
-m = np.zeros(n, dtype=msg)
-m["rtype"], m["txn_id"], m["batch_id"] = L.WIRE_CL_QRY, (1 << 64) - 1, (1 << 64) - 1
-m["mq"], m["lat"] = 12345, 0.5  # (clocks the sequencer zeroes)
-m["cst"] = 1_000_000 + np.arange(n, dtype=np.uint64)
-m["np"], m["part"], m["nreq"] = 1, 0, R
-m["req"]["acc"], m["req"]["key"] = ep.types.reshape(n, R), ep.keys.reshape(n, R)
-per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // msg.itemsize
-raw = m.view(np.uint8).reshape(n, msg.itemsize)
-mbufs = [struct.pack("<III", NODE, nodes + (s // per) % n_clients, min(n, s + per) - s) + raw[s:s + per].tobytes()
-         for s in range(0, n, per)]
+# ---- the receive queue: the clients' mbufs of a CALVIN build (84-byte header)
+def ycsb_mbufs():
+    """numpy all the way"""
+    gen = dvcc.YCSBQueryGenerator(rows, part_cnt=part_cnt, req_per_query=R, zipf_theta=0.6, txn_write_perc=1.0,
+                                  tup_write_perc=0.5, part_per_txn=min(part_cnt, 2), strict_ppt=0, mpr=-1.0)
+    ep = gen.gen(n, dvcc.epoch_seed(0, 7))
+    assert (np.diff(ep.txn_begin.astype(np.int64)) == R).all()
+    req = np.dtype([("acc", "<u4"), ("pad", "<u4"), ("key", "<u8"), ("val", "u1"), ("pad2", "u1", (7,))])
+    # (every query names one partition here, whatever its keys: the sequencer routes by the keys, the list is only checked)
+    msg = np.dtype([("rtype", "<u4"), ("txn_id", "<u8"), ("batch_id", "<u8"), ("mq", "<u8"), ("lat", "<f8", (7,)),
+                    ("cst", "<u8"), ("np", "<u8"), ("part", "<u8"), ("nreq", "<u8"), ("req", req, (R,))], align=False)
+    m = np.zeros(n, dtype=msg)
+    m["rtype"], m["txn_id"], m["batch_id"] = L.WIRE_CL_QRY, (1 << 64) - 1, (1 << 64) - 1
+    m["mq"], m["lat"] = 12345, 0.5  # (clocks the sequencer zeroes)
+    m["cst"] = 1_000_000 + np.arange(n, dtype=np.uint64)
+    m["np"], m["part"], m["nreq"] = 1, 0, R
+    m["req"]["acc"], m["req"]["key"] = ep.types.reshape(n, R), ep.keys.reshape(n, R)
+    per = (L.WIRE_MSG_MAX - L.WIRE_HDR) // msg.itemsize
+    raw = m.view(np.uint8).reshape(n, msg.itemsize)
+    mbufs = [struct.pack("<III", NODE, nodes + (s // per) % n_clients, min(n, s + per) - s) + raw[s:s + per].tobytes()
+             for s in range(0, n, per)]
+    return mbufs
+
+
+def tpcc_mbufs(pp):
+    """the generated queries, a message each, packed greedily per client in runs of 16"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import wire_fmt as W
+    qs = DW.tpcc_gen_queries(pp, n, 7)
+    msgs = []
+    for i in range(n):
+        x = qs[i]
+        m_ = W.tpcc_query(dict(
+            txn_type=x.txn_type, w_id=x.w_id, d_id=x.d_id, c_id=x.c_id, d_w_id=x.d_w_id, c_w_id=x.c_w_id,
+            c_d_id=x.c_d_id, c_last=bytes(x.c_last), h_amount=x.h_amount, by_last_name=x.by_last_name,
+            ol_cnt=x.ol_cnt, o_entry_d=x.o_entry_d, rbk=x.rbk, remote=x.remote,
+            parts=[x.parts[j] for j in range(x.n_parts)],
+            items=[(x.items[j].ol_i_id, x.items[j].ol_supply_w_id, x.items[j].ol_quantity) for j in range(x.ol_cnt)]),
+            1_000_000 + i, W.U64_MAX, W.U64_MAX)
+        msgs.append(m_[:20] + struct.pack("<Q", 12345) + struct.pack("<7d", *(0.5,) * 7) + m_[84:])  # (clocks to zero)
+    out = []
+    for s_ in range(0, n, 16):
+        out += W.batches(NODE, nodes + (s_ // 16) % n_clients, msgs[s_:s_ + 16])
+    return out
+
+
+pp = tpcc_params(32, part_cnt=nodes) if tpcc else None
+mbufs = tpcc_mbufs(pp) if tpcc else ycsb_mbufs()
 off = np.zeros(len(mbufs) + 1, np.uint64)
 off[1:] = np.cumsum([len(b) for b in mbufs])
 buf = np.frombuffer(b"".join(mbufs), np.uint8)
 in_bytes, nb_in = len(buf), len(mbufs)
 
 eng = dvcc.CCEngine("CALVIN", 1024, 1024)
-cfg = DW._seq_cfg(NODE, nodes, part_cnt, rows, 0)
+cfg = DW._seq_cfg(NODE, nodes, part_cnt, rows, 0, pp) if tpcc else DW._seq_cfg(NODE, nodes, part_cnt, rows, 0)
 lib = L.lib()
 d_buf = torch.from_numpy(buf.copy()).cuda()
 d_off = torch.from_numpy(off.view(np.int64)).cuda()
 
 # the sizes from one host call with room to spare; then exact capacities for every leg
 probe = DW.sequence_host(buf, off, E, node_id=NODE, node_cnt=nodes, part_cnt=part_cnt, synth_table_size=rows,
-                         n_dest=n_dest, max_txn=n).result
+                         n_dest=n_dest, max_txn=n, **(dict(params=pp) if tpcc else {})).result
 assert probe.status == L.DV_OK and probe.n_txn == n
 cap, max_b = probe.n_bytes, probe.n_out
 
@@ -185,12 +224,12 @@ for _ in range(args.reps * args.iters):
 kt = eng.kernel_times(reset=True)
 eng.set_timing(False)
 kernels_us = {k: round(ms / cnt * 1e3, 2) for k, (cnt, ms) in sorted(kt.items(), key=lambda kv: -kv[1][1])}
-emit_us = kernels_us.get("k_seq_emit")
-cut_us = sum(kernels_us.get(k, 0) for k in ("k_seq_tiles", "k_seq_chain", "k_seq_marks"))
+emit_us = kernels_us.get("k_seq_emit_bytes" if tpcc else "k_seq_emit")
+cut_us = sum(kernels_us.get(k, 0) for k in ("k_seq_tiles", "k_seq_chain", "k_seq_marks_bytes" if tpcc else "k_seq_marks"))
 
 best, worst = {k: min(v) for k, v in runs.items()}, {k: max(v) for k, v in runs.items()}
 out = {
-    "shape": args.shape, "txns": n, "nodes": nodes, "part_cnt": part_cnt, "client_mbufs": nb_in, "in_bytes": in_bytes,
+    "shape": args.shape, "workload": args.workload, "txns": n, "nodes": nodes, "part_cnt": part_cnt, "client_mbufs": nb_in, "in_bytes": in_bytes,
     "messages_out": int(res_a.n_msgs), "mbufs_out": int(res_a.n_out), "out_bytes": int(res_a.n_bytes),
     "device": torch.cuda.get_device_name(0), "reps": args.reps, "iters": args.iters,
     "a_host_one_core_with_copies_ms": [best["a"], worst["a"]], "b_device_plus_d2h_ms": [best["b"], worst["b"]],
